@@ -1,25 +1,30 @@
 #!/usr/bin/env python3
 """bench.py -- SRF training-step throughput (acoustic frames/sec) on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Headline workload (the metric's "3-iter DR at 1/2/4/8 MI355X" = BASELINE.json
 configs[3], C4, whose per-GPU batch fits one GPU): WSJ SRF L=6, PH=CH=16, DIM=32,
 LPAD=RPAD=2, DR iter 3, fp32, class_n 32; per GPU B=28 utterances of T=800 frames
-(the reference's bucket rule for 24000 frames/batch).  The TIMIT C2
-model (configs[1]: L=3, PH=CH=8, DIM=16, LPAD=RPAD=4, B=17, T=320) is measured
-after it and reported under "extra".  Synthetic N(0,1) 123-d fbank, labels
-uniform in [1, C-2], L = T'/2.
+(the reference's bucket rule for 24000 frames/batch).  Synthetic
+N(0,1) 123-d fbank, labels uniform in [1, C-2], L = T'/2.
 One step = process_train_step: crop, forward, CTC, backward, RCCL gradient
 all-reduce (N > 1), fused Adam.  value = sum(inp_len) over all ranks / step time
 (the reference's frame counter, trainer_sr.py:74), weak scaling.
 
-Prints ONE JSON line on rank 0 (roofline of the dominant kernel from HIP events
-inside the timed region; CPU baseline = torch-CPU op-for-op mirror of
-sequence_router_naive.py on a bounded sample, rank 0 at N=1 only, on all host
-threads and on one core).
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0
+(metric, value, unit, ms_per_step, dtype, config).  --dump-outputs DIR also writes what
+the last timed step computed (rank 0: DIR/nll.npy, DIR/grad.npy;
+that step starts from the initial parameters again, see dump_outputs).
+
+--full adds everything else to that line, each measured outside the timed steps: the
+roofline of the dominant kernel (HIP events around it in eager steps), forward-only
+frames/s, the CPU baseline (torch-CPU op-for-op mirror of sequence_router_naive.py on
+a bounded sample, rank 0 at N=1 only, on all host threads and on one core), and the
+--extra workloads (default: the TIMIT C2 model, configs[1]: L=3, PH=CH=8, DIM=16,
+LPAD=RPAD=4, B=17, T=320).
 """
 import argparse
 import ctypes
@@ -28,6 +33,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -45,6 +51,7 @@ WORKLOADS = {
     'wsj_c5_fp8': (dict(enc=8, iters=5, lpad=20, rpad=20, ph=16, pd=64, ch=16, cd=64, vd=64, context=True,
                         pose_fp8=True), 32, 28, 800),
 }
+DUMP_MAX_BYTES = 64 * 10 ** 6   # --dump-outputs: all files together stay below this
 FP32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: FP32 matrix (= vector) peak
 BF16_MFMA_PEAK_TFLOPS = 2500.0  # dense bf16 / f16 MFMA peak
 HBM_PEAK_GBS = 8000.0
@@ -193,15 +200,46 @@ def pmc_traffic(path, kernels, weights):
     return total / sum(weights)
 
 
-def _timed(step, steps, world, dev):
-    """Barrier + synchronize on both sides of `steps` calls; max over ranks."""
+def dump_outputs(out_dir, nll, model):
+    """What a caller of the timed step holds after it: the per-utterance CTC NLL it
+    returns and the gradient it left in the model (flat, in the model's parameter
+    order), as float32 .npy files.  An array over its share of DUMP_MAX_BYTES is stored
+    as a fixed, seeded sample of its elements (in index order).
+
+    The batch and the dropout seeds are the same in every run with the same arguments,
+    and measure() puts the seeded initial parameters back before the last timed step, so
+    that step computes from the same state in every run: training steps amplify the
+    rounding of the kernels' float atomics (their sums reorder from launch to launch),
+    and parameters carried through the warm-up and the earlier timed steps made two runs
+    of one build differ by 2.5e-3 of max |grad|.  What is left between two runs is one
+    step's rounding.  The Adam update that follows is not dumped: on fresh moments it is
+    alpha * sign(g), ill-conditioned wherever a gradient sum cancels, and it is an
+    elementwise function of the gradient dumped here."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'nll': nll, 'grad': model.flat_grad}
+    cap = (DUMP_MAX_BYTES - (1 << 16)) // len(arrays) // 4   # float32 elements per file, headers aside
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy().reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(20240 + len(name)).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def _timed(step, steps, world, dev, last=None, before_last=None):
+    """Barrier + synchronize on both sides of `steps` calls; max over ranks.  `last`
+    (a list) receives what the final call returned; `before_last()` runs ahead of it."""
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        step()
+    ret = None
+    for i in range(steps):
+        if before_last is not None and i == steps - 1:
+            before_last()
+        ret = step()
     torch.cuda.synchronize()
+    if last is not None:
+        last.append(ret)
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
@@ -241,17 +279,20 @@ def sdr_roofline(model, tms, group=1):
                                                                                      reads)}
 
 
-def measure(workload, args, world, rank, dev, flag_group=None):
+def measure(workload, args, world, rank, dev, flag_group=None, dump_dir=None):
     """One workload: W eager + W graphed warmup steps, K timed training steps (the
-    hipGraph replay of forward + CTC + backward, then the all-reduce and Adam), K
-    eager steps with HIP events around the last layer's forward routing passes,
-    and K forward-only passes."""
+    hipGraph replay of forward + CTC + backward, then the all-reduce and Adam), whose
+    last outputs go to `dump_dir` when one is given; with --full also K eager steps
+    with HIP events around the last layer's forward routing passes, and K forward-only
+    passes."""
     from srf_amd import train_helper, trainer_sr
     from srf_amd.sequence_router import SequenceRouter
 
     kw, class_n, B, T = WORKLOADS[workload]
     cfg = make_config(kw)
     model = SequenceRouter(cfg, None, class_n, device=dev, seed=1234)   # same init on every rank
+    # --dump-outputs: the last timed step starts from these parameters again (dump_outputs)
+    init_params = model.flat_params.clone() if dump_dir else None
     if args.sdr_separate_gxgw:
         from srf_amd import ops
         ops.SDR_FUSED_GXGW = False
@@ -286,7 +327,8 @@ def measure(workload, args, world, rank, dev, flag_group=None):
     loss_state, frame_state, samples = trainer_sr.Mean(), trainer_sr.Mean(), trainer_sr.Sum()
 
     def eager_step():
-        trainer_sr.process_train_step(4, batch, model, opt, loss_state, frame_state, world, class_n - 1, samples)
+        return trainer_sr.process_train_step(4, batch, model, opt, loss_state, frame_state, world, class_n - 1,
+                                             samples)
 
     for _ in range(args.warmup):
         eager_step()
@@ -317,7 +359,7 @@ def measure(workload, args, world, rank, dev, flag_group=None):
         torch.cuda.synchronize()
 
         def step():
-            graphed(loss_state, frame_state, samples)
+            return graphed(loss_state, frame_state, samples)
 
     # HIP events around the dominant kernel (forward routing passes of the last
     # layer), recorded on the launch stream
@@ -327,13 +369,17 @@ def measure(workload, args, world, rank, dev, flag_group=None):
     geom = model._geom(last, B, Tp)
     R = model.iter
     dr = not model.is_context    # the event hook times DR passes; SDR runs no such pass
-    ev_pairs = [(ev.create(R), ev.create(R)) for _ in range(args.steps)] if dr else []
-    if dr and args.eager:
+    ev_pairs = [(ev.create(R), ev.create(R)) for _ in range(args.steps)] if (dr and args.full) else []
+    if ev_pairs and args.eager:
         geom.timing = [(ctypes.cast(a, ctypes.c_void_p), ctypes.cast(b, ctypes.c_void_p), R) for a, b in ev_pairs]
 
-    elapsed = _timed(step, args.steps, world, dev)
+    final = []
+    elapsed = _timed(step, args.steps, world, dev, final,
+                     (lambda: model.flat_params.copy_(init_params)) if dump_dir else None)
     geom.timing = None
-    if dr and not args.eager:
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, final[0], model)
+    if ev_pairs and not args.eager:
         # graph replays carry no per-kernel events: time the same kernels in as many
         # eager steps right after the timed region (same shapes, same stream)
         geom.timing = [(ctypes.cast(a, ctypes.c_void_p), ctypes.cast(b, ctypes.c_void_p), R) for a, b in ev_pairs]
@@ -343,6 +389,26 @@ def measure(workload, args, world, rank, dev, flag_group=None):
         geom.timing = None
     if graphed is not None:
         graphed.close()
+
+    from srf_amd import ops
+    res = {
+        'value': round(B * T * world * args.steps / elapsed, 1), 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
+        'config': {'workload': f'{workload}: SRF L={cfg.model_encoder_num} PH=CH={cfg.model_caps_primary_num} '
+                               f'DIM={cfg.model_caps_primary_dim} LPAD=RPAD={cfg.model_caps_window_lpad} '
+                               f'{"SDR" if model.is_context else "DR"} iter={cfg.model_caps_iter}, '
+                               f'{"fp8 (e4m3) pose MFMA, " if model.pose_fp8 else ""}'
+                               f'train step (fwd+bwd+allreduce+Adam)',
+                   'utterances_per_gpu': B, 'frames_per_utterance': T, 'global_batch': B * world,
+                   'parallelism': f'dp{world}',
+                   'allreduce': (None if world == 1 else
+                                 'RCCL SUM in 25 MB buckets launched as the backward completes them, captured in '
+                                 'the step graph' if bucketed else 'one flat RCCL SUM after each replay'),
+                   'launch': 'eager' if args.eager else 'hipgraph (fwd+CTC+bwd)'},
+        'dtype': 'fp8 pose (e4m3, fp32 accumulate) / fp32' if model.pose_fp8 else 'fp32',
+    }
+    if not args.full:
+        ops.check_faults()   # a grouped SDR recurrence that timed out made this run's results wrong
+        return res, model, cfg, class_n, T
 
     # forward-only frames/s: model(feats, training=False) as in
     # process_valid_step (BN moving statistics, no dropout), eager launches, outside
@@ -387,19 +453,7 @@ def measure(workload, args, world, rank, dev, flag_group=None):
     rpass = f'void route_fwd32{"p" if tw <= 2 else ""}_kernel<{Din}, {D}, 8, {tw}>'
     if fwd32 and traffic_src:
         traffic = pmc_traffic(traffic_src, [first, rpass], [1.0, R - 1.0])
-    res = {
-        'value': round(B * T * world * args.steps / elapsed, 1), 'ms_per_step': round(elapsed / args.steps * 1e3, 4),
-        'config': {'workload': f'{workload}: SRF L={cfg.model_encoder_num} PH=CH={cfg.model_caps_primary_num} '
-                               f'DIM={cfg.model_caps_primary_dim} LPAD=RPAD={cfg.model_caps_window_lpad} '
-                               f'{"SDR" if model.is_context else "DR"} iter={cfg.model_caps_iter}, '
-                               f'{"fp8 (e4m3) pose MFMA, " if model.pose_fp8 else ""}'
-                               f'train step (fwd+bwd+allreduce+Adam)',
-                   'utterances_per_gpu': B, 'frames_per_utterance': T, 'global_batch': B * world,
-                   'parallelism': f'dp{world}',
-                   'allreduce': (None if world == 1 else
-                                 'RCCL SUM in 25 MB buckets launched as the backward completes them, captured in '
-                                 'the step graph' if bucketed else 'one flat RCCL SUM after each replay'),
-                   'launch': 'eager' if args.eager else 'hipgraph (fwd+CTC+bwd)'},
+    res.update({
         'roofline': {'kernel': (f'{first.replace("void ", "")} + {rpass.replace("void ", "")} (layer {last + 1} DR '
                                 f'forward passes, R={R}; pose on v_mfma_f32_32x32x16_f16 as 2-term fp16 splits of '
                                 f'power-of-two scaled operands + one bf16 bias MFMA = fp32-accurate)'
@@ -420,12 +474,10 @@ def measure(workload, args, world, rank, dev, flag_group=None):
                                                       * {8: 3, 16: 4, 32: 7}[Din] / (kern_avg_ms * 1e-3) / 1e12
                                                       / BF16_MFMA_PEAK_TFLOPS, 4)} if fwd32 else None)}
                     if dr else sdr_roof,
-        'dtype': 'fp8 pose (e4m3, fp32 accumulate) / fp32' if model.pose_fp8 else 'fp32',
         'forward_only': {'value': round(B * T * world * args.steps / fwd_elapsed, 1), 'unit': 'frames/s',
                          'ms_per_step': round(fwd_elapsed / args.steps * 1e3, 4),
                          'mode': 'model(feats, training=False), eager launches'},
-    }
-    from srf_amd import ops
+    })
     ops.check_faults()   # a grouped SDR recurrence that timed out made this run's results wrong
     return res, model, cfg, class_n, T
 
@@ -437,10 +489,15 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--workload', default='wsj_c4', choices=sorted(WORKLOADS),
                     help='the headline line (BASELINE metric: 3-iter DR on the WSJ C4 model)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed to DIR/{nll,grad}.npy (float32; rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure, outside the timed steps, the dominant kernel\'s roofline, forward-only '
+                         'frames/s, the CPU baseline and the --extra workloads')
     ap.add_argument('--extra', default='timit_c2',
-                    help='comma-separated workloads also measured, reported under "extra" (empty: none)')
-    ap.add_argument('--cpu-seconds', type=float, default=15.0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+                    help='--full: comma-separated workloads also measured, reported under "extra" (empty: none)')
+    ap.add_argument('--cpu-seconds', type=float, default=15.0, help='--full: length of the CPU baseline run')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave the CPU baseline out')
     ap.add_argument('--sdr-last-group', default=None,
                     help='SDR stack: workgroups per utterance of the last layer\'s recurrence, "G" or '
                          '"G_forward,G_backward" (default: SdrStackPlan.group)')
@@ -482,16 +539,18 @@ def main():
     flag_group = None
     if world > 1:
         flag_group = dist.group.WORLD if backend == 'gloo' else dist.new_group(backend='gloo')
-    res, model, cfg, class_n, T = measure(args.workload, args, world, rank, dev, flag_group)
+    res, model, cfg, class_n, T = measure(args.workload, args, world, rank, dev, flag_group, args.dump_outputs)
     line = {
         'metric': 'acoustic frames/sec through SRF (123-d fbank, 3-iter DR) at 1/2/4/8 MI355X',
         'value': res['value'], 'unit': 'frames/s', 'n_gpus': world, 'steps': args.steps,
         'warmup': args.warmup, 'ms_per_step': res['ms_per_step'], 'higher_is_better': True,
         'scaling': 'weak', 'vs_baseline': None, 'dtype': res['dtype'],
         'data': 'synthetic (N(0,1) 123-d fbank, random init)',
-        'config': res['config'], 'roofline': res['roofline'], 'forward_only': res['forward_only'],
+        'config': res['config'],
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        line['roofline'], line['forward_only'] = res['roofline'], res['forward_only']
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the full host (every usable core: affinity mask within the cgroup quota) on one utterance of the workload's
         # length, and one core on a quarter-length utterance (frames/s is per frame)
         cb = cpu_baseline(model, cfg, class_n, T, args.cpu_seconds)
@@ -499,7 +558,7 @@ def main():
         cb['one_core'] = {k: one[k] for k in ('value', 'cores', 'sample')}
         line['cpu_baseline'] = cb
     del model
-    extra = [w for w in args.extra.split(',') if w and w != args.workload]
+    extra = [w for w in args.extra.split(',') if w and w != args.workload] if args.full else []
     if extra:
         line['extra'] = {}
         for w in extra:

@@ -6,10 +6,10 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/${TAG:-benchall}
 mkdir -p $OUT
 CB=--no-cpu-baseline
 [ -n "$CPU" ] && CB=
-timeout -k 10 400 python -u bench.py $CB > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
-timeout -k 10 300 python -u bench.py --workload wsj_c3 --extra= --no-cpu-baseline --steps 10 --warmup 2 \
+timeout -k 10 400 python -u bench.py --full $CB > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+timeout -k 10 300 python -u bench.py --full --workload wsj_c3 --extra= --no-cpu-baseline --steps 10 --warmup 2 \
   > $OUT/c3.json 2> $OUT/c3.err || { tail -5 $OUT/c3.err; exit 2; }
-timeout -k 10 600 python -u bench.py --workload wsj_c5 --extra= --no-cpu-baseline --steps 2 --warmup 1 \
+timeout -k 10 600 python -u bench.py --full --workload wsj_c5 --extra= --no-cpu-baseline --steps 2 --warmup 1 \
   > $OUT/c5.json 2> $OUT/c5.err || { tail -5 $OUT/c5.err; exit 3; }
 python - <<PY
 import json

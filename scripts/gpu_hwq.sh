@@ -6,8 +6,8 @@ cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${TAG:-hwq}
 mkdir -p $OUT
 for q in 4 16 32; do
-  GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --workload wsj_c3 --extra= --no-cpu-baseline --steps 10 --warmup 2 > $OUT/c3_q$q.json 2> $OUT/c3_q$q.err || exit 1
-  GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --workload wsj_c5 --extra= --no-cpu-baseline --steps 2 --warmup 1 > $OUT/c5_q$q.json 2> $OUT/c5_q$q.err || exit 2
+  GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --full --workload wsj_c3 --extra= --no-cpu-baseline --steps 10 --warmup 2 > $OUT/c3_q$q.json 2> $OUT/c3_q$q.err || exit 1
+  GPU_MAX_HW_QUEUES=$q timeout -k 10 300 python -u bench.py --full --workload wsj_c5 --extra= --no-cpu-baseline --steps 2 --warmup 1 > $OUT/c5_q$q.json 2> $OUT/c5_q$q.err || exit 2
   python -c "
 import json
 for w in ('c3', 'c5'):

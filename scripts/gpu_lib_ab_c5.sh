@@ -7,6 +7,6 @@ mkdir -p $OUT
 for lib in default $LIBS; do
   n=$(basename $lib .so)
   if [ $lib = default ]; then unset SRF_LIB_PATH; else export SRF_LIB_PATH=$GRAFT_REPO_ROOT/$lib; fi
-  timeout -k 10 300 python -u bench.py --workload ${WL:-wsj_c5} --extra= --no-cpu-baseline --steps 2 --warmup 1 > $OUT/$n.json 2> $OUT/$n.err || { tail -3 $OUT/$n.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --workload ${WL:-wsj_c5} --extra= --no-cpu-baseline --steps 2 --warmup 1 > $OUT/$n.json 2> $OUT/$n.err || { tail -3 $OUT/$n.err; exit 1; }
   python -c "import json; d=json.load(open('$OUT/$n.json')); r=d['roofline']; print('$n', d['ms_per_step'], d['forward_only']['ms_per_step'], r and r['avg_launch_us'])"
 done

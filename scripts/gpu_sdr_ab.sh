@@ -6,7 +6,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/${TAG:-sdrab}
 mkdir -p $OUT
 run() {  # name steps workload extra-args...
   local n=$1 st=$2 wl=$3; shift 3
-  timeout -k 10 300 env "$@" python -u bench.py --workload $wl --extra= --no-cpu-baseline --steps $st --warmup 2 $EAGER > $OUT/$n.json 2> $OUT/$n.err || exit 1
+  timeout -k 10 300 env "$@" python -u bench.py --full --workload $wl --extra= --no-cpu-baseline --steps $st --warmup 2 $EAGER > $OUT/$n.json 2> $OUT/$n.err || exit 1
   python -c "import json; d=json.load(open('$OUT/$n.json')); print('$n', d['ms_per_step'], d['forward_only']['ms_per_step'])"
 }
 EAGER=--eager run c3_eager_q4 10 wsj_c3 GPU_MAX_HW_QUEUES=4
