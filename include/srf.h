@@ -33,11 +33,24 @@ const char* srf_last_error(void);
  * window :150-151, tile+matmul pose :154-159, tf.while_loop DR :171-185 with
  * _loop_body :199-206) and, for the backward, its TF autodiff.
  * mask_first = 1 for the last layer (the -1e9 logit mask on capsule 0,
- * naive:173-178).  n_chunks splits the input capsules over workgroups
- * (srf_route_dr_auto_chunks gives the tuned default).
+ * naive:173-178).  n_chunks is the plan argument: how the input capsules are
+ * split over workgroups, either 1 .. in_n uniform chunks or the opaque value
+ * srf_route_dr_auto_chunks returns (the tuned default; it may encode a balanced
+ * split, and is > 1 whenever the work is split).
  * saved: 2*iters*B*T*J*dout floats written by the forward and read by the
- * backward (s^r and the accumulated agreement vector after each iteration). */
+ * backward (s^r and the accumulated agreement vector after each iteration;
+ * the last plane, the vector after the last iteration, has no reader and is
+ * not written by layers with more than one iteration). */
 int srf_route_dr_auto_chunks(int B, int T, int N, int din, int lpad, int rpad, int J, int dout);
+/* Host only (no device needed): the work split that plan argument n_chunks (0: the
+ * default) gives the routing passes r >= 1 of a 32x32-pass shape.  info[5] =
+ * {balanced, workgroups, units = frame tiles * in_n, slab slots per frame tile, the
+ * plan argument in srf_route_dr_auto_chunks' encoding}; table receives up to `capacity`
+ * rows {workgroup, frame tile, i0, i1, slab slot}, one per segment, in the order the
+ * workgroups walk them.  Returns the number of segments (which may exceed capacity);
+ * other shapes are an error. */
+int srf_route_dr_split_table(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks,
+                             int* info, int* table, int capacity);
 size_t srf_route_dr_saved_floats(int B, int T, int J, int dout, int iters);
 size_t srf_route_dr_fwd_workspace(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters,
                                   int n_chunks);

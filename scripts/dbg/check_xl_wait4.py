@@ -1,9 +1,10 @@
 """Check the x_dma waits of the four-row-tile passes (route_fwd32_kernel /
 route_bwd32_kernel <32,32,NW,4>) against their ISA.  There the DMA of capsule i + 2 is
 issued after capsule i's barrier and waited for (xl_wait) before capsule i + 1's, so the
-walk from each in-loop global_load_lds to the next s_barrier wraps around the loop's
-back edge: the last 's_waitcnt vmcnt(K)' on that walk must leave at most as many
-vector-memory operations in flight as the wave issued after the DMA.
+walk from each global_load_lds of the capsule loop (the innermost loop, inside the
+workgroup's segment loop) to the next s_barrier wraps around the loop's back edge: the
+last 's_waitcnt vmcnt(K)' on that walk must leave at most as many vector-memory
+operations in flight as the wave issued after the DMA.
     python scripts/dbg/check_xl_wait4.py ISA.s"""
 import re
 import sys
@@ -14,7 +15,11 @@ for name in re.findall(r'^(_Z\w*route_(?:fwd|bwd)32_kernelILi32ELi32ELi[248]ELi4
     body = s[s.index(name + ':'):]
     body = body[:body.index('.Lfunc_end')]
     raw = body.split('\n')
-    hdr = [k for k, l in enumerate(raw) if 'Loop Header' in l and 'Depth=1' in l]
+    # the capsule loop: the innermost one (inside the segment loop of the workgroup); its
+    # label stands on the header comment's line or on a line before it
+    hdr = [k for k, l in enumerate(raw) if 'Inner Loop Header' in l][:1]
+    while not re.match(r'\.LBB\d+_\d+:', raw[hdr[0]]):
+        hdr[0] -= 1
     lab = raw[hdr[0]].split(':')[0]
     ends = [k for k, l in enumerate(raw) if 'branch' in l and l.strip().endswith(lab)]
     lo, hi = min(hdr + ends), max(hdr + ends)

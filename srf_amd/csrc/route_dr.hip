@@ -1844,29 +1844,47 @@ __device__ __forceinline__ float qsum(float v) {
   return v;
 }
 
-__device__ __forceinline__ f4 sum_slab4(const float* __restrict__ slab, int n, size_t FJD, size_t off) {
+// How many partial slabs hold a frame's sum: n for every frame (uniform i-chunks), or,
+// for the balanced split of the 32x32 passes (G > 0, route_fwd32.h), the segments of the
+// frame's 32-frame tile, from the same arithmetic the passes use.  The order of the sum
+// is the slot order: fixed for a given plan.
+struct SlabSplit {
+  int n;
+  int G, U, in_n, JD;
+};
+
+__device__ __forceinline__ int slab_count(const SlabSplit& sp, size_t FJD, size_t off) {
+  if (sp.G <= 0) return sp.n;
+  const uint32_t f = FJD <= 0xffffffffu ? (uint32_t)off / (uint32_t)sp.JD : (uint32_t)(off / (size_t)sp.JD);
+  return srf::bal_tile_slots((int)(f >> 5), sp.in_n, sp.U, sp.G);
+}
+
+__device__ __forceinline__ f4 sum_slab4(const float* __restrict__ slab, const SlabSplit& sp, size_t FJD, size_t off) {
+  const int n = slab_count(sp, FJD, off);
   f4 a = ld4(slab + off);
 #pragma unroll 4
   for (int c = 1; c < n; ++c) a += ld4(slab + (size_t)c * FJD + off);
   return a;
 }
 
-// s^r = sum over i-chunks; v^r = squash(s^r) (naive:204); Vc^{r+1} = Vc^r + v^r.
+// s^r = sum over the partial slabs; v^r = squash(s^r) (naive:204); Vc^{r+1} = Vc^r + v^r.
 template <int DOUT>
-__global__ void fwd_finish_kernel(const float* __restrict__ slab, int n_chunks, size_t FJD,
+__global__ void fwd_finish_kernel(const float* __restrict__ slab, SlabSplit sp, size_t FJD,
                                   const float* __restrict__ vc_in, float* __restrict__ s_out,
                                   float* __restrict__ vc_out, float* __restrict__ v_out) {
   constexpr int Q = DOUT / 4;
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // float4 index; FJD/4 % Q == 0
   const bool ok = idx < FJD / 4;
   const size_t off = (ok ? idx : 0) * 4;
-  const f4 sv = sum_slab4(slab, n_chunks, FJD, off);
+  const f4 sv = sum_slab4(slab, sp, FJD, off);
   const float n2 = qsum<Q>((sv.x * sv.x + sv.y * sv.y) + (sv.z * sv.z + sv.w * sv.w));
   if (!ok) return;
   const float fac = n2 / (1.f + n2) / sqrtf(n2 + kSquashEps);
   const f4 v = sv * fac;
   st4(s_out + off, sv);
-  st4(vc_out + off, vc_in ? v + ld4(vc_in + off) : v);
+  // vc_out == nullptr (the last iteration): nothing reads Vc^R, so neither Vc^{R-1} is
+  // loaded nor Vc^R stored
+  if (vc_out) st4(vc_out + off, vc_in ? v + ld4(vc_in + off) : v);
   if (v_out) st4(v_out + off, v);
 }
 
@@ -1874,7 +1892,7 @@ __global__ void fwd_finish_kernel(const float* __restrict__ slab, int n_chunks, 
 // iteration's v) or, for earlier iterations, a = A += sum of gVc slabs.
 // zero4 / nz4: float4s zeroed by the same launch (the g_emb accumulator of the gu pass).
 template <int DOUT>
-__global__ void bwd_finish_kernel(const float* __restrict__ slab, int n_chunks, size_t FJD,
+__global__ void bwd_finish_kernel(const float* __restrict__ slab, SlabSplit sp, size_t FJD,
                                   const float* __restrict__ a_init, float* __restrict__ A,
                                   const float* __restrict__ s, float* __restrict__ gs, float* __restrict__ zero4,
                                   size_t nz4, float* __restrict__ zero1) {
@@ -1889,7 +1907,7 @@ __global__ void bwd_finish_kernel(const float* __restrict__ slab, int n_chunks, 
     a = ld4(a_init + off);
     if (ok) st4(A + off, f4{0.f, 0.f, 0.f, 0.f});   // A starts at 0 (gradient via later logits)
   } else {
-    a = ld4(A + off) + sum_slab4(slab, n_chunks, FJD, off);
+    a = ld4(A + off) + sum_slab4(slab, sp, FJD, off);
     if (ok) st4(A + off, a);
   }
   const f4 sv = ld4(s + off);
@@ -1975,21 +1993,21 @@ void dispatch_pass(const Geom& g, const PassCfg& pc, int n_chunks, const float* 
 }
 
 template <int D>
-void launch_fwd_finish(const Geom& g, const float* slab, int n_chunks, const float* vc_in, float* s_out,
+void launch_fwd_finish(const Geom& g, const float* slab, const SlabSplit& sp, const float* vc_in, float* s_out,
                        float* vc_out, float* v_out, hipStream_t st) {
   const size_t FJD = (size_t)g.F() * g.JD();
-  hipLaunchKernelGGL((fwd_finish_kernel<D>), dim3((FJD / 4 + 255) / 256), dim3(256), 0, st, slab, n_chunks, FJD,
+  hipLaunchKernelGGL((fwd_finish_kernel<D>), dim3((FJD / 4 + 255) / 256), dim3(256), 0, st, slab, sp, FJD,
                      vc_in, s_out, vc_out, v_out);
 }
 
 template <int D>
-void launch_bwd_finish(const Geom& g, const float* slab, int n_chunks, const float* a_init, float* A,
+void launch_bwd_finish(const Geom& g, const float* slab, const SlabSplit& sp, const float* a_init, float* A,
                        const float* s, float* gs, hipStream_t st, float* zero = nullptr, size_t n_zero = 0,
                        float* zero1 = nullptr) {
   const size_t FJD = (size_t)g.F() * g.JD();
   const size_t nz4 = zero ? n_zero / 4 : 0;
   const size_t n = std::max(FJD / 4, nz4);
-  hipLaunchKernelGGL((bwd_finish_kernel<D>), dim3((n + 255) / 256), dim3(256), 0, st, slab, n_chunks, FJD, a_init,
+  hipLaunchKernelGGL((bwd_finish_kernel<D>), dim3((n + 255) / 256), dim3(256), 0, st, slab, sp, FJD, a_init,
                      A, s, gs, zero, nz4, zero1);
 }
 
@@ -2241,6 +2259,23 @@ int launch_gw2(const Geom& g, const Gw2Plan& p, const float* xT, const float* sa
 // route_pass_kernel (exact fp32 16x16x4 tiles) the others (din 64, J*dout > 1024).
 inline bool use_fwd32(const Geom& g) { return srf::fwd32_supported(g.din, g.dout, g.J); }
 
+// The plan argument n_chunks of the entry points (route_fwd32.h): 1 .. in_n uniform
+// i-chunks, or srf::kBalFlag | G, the balanced split, which only the 32x32 passes have.
+inline bool plan_balanced(int n_chunks) { return n_chunks > 0 && (n_chunks & srf::kBalFlag) != 0; }
+inline bool plan_arg_ok(const Geom& g, int n_chunks) {
+  return plan_balanced(n_chunks) ? use_fwd32(g) : (n_chunks >= 1 && n_chunks <= g.in_n());
+}
+// i-chunks of the exact-fp32 passes (route_pass_kernel): under a balanced plan they run
+// only a backward without stored couplings, with their own cost model's chunk count
+inline int legacy_chunks(const Geom& g, int n_chunks) {
+  return plan_balanced(n_chunks) ? auto_chunks(g, pass_cfg(g).NW) : n_chunks;
+}
+inline SlabSplit uniform_split(int n) { return SlabSplit{n, 0, 0, 0, 0}; }
+// the slabs of a 32x32 pass r >= 1
+inline SlabSplit pass_split(const Geom& g, const srf::Fwd32Plan& p) {
+  return p.bal_G > 0 ? SlabSplit{p.n_slots, p.bal_G, p.bal_U, g.in_n(), g.JD()} : uniform_split(p.n_chunks);
+}
+
 // Coupling storage is used when the split-bf16 forward runs and the gu pass from
 // stored couplings (route_gux_kernel) fits its window accumulator in LDS; otherwise
 // the forward keeps nothing and the backward recomputes (round-1 kernels).
@@ -2328,10 +2363,12 @@ int fwd_impl(const Geom& g, int n_chunks, const float* emb, const float* W, cons
     }
     SRF_LAUNCH_CHECK("route_pass(fwd)");
     if (r < nev) SRF_HIP_TRY(hipEventRecord(ev1[r], st));
+    // the last iteration stores no Vc^R (plane 2R - 1 of saved): nothing reads it
+    const bool last = r == g.iters - 1;
     launch_fwd_finish<D>(g, p32 ? srf::fwd32_slab(plan, scratch) : slab,
-                         p32 ? plan.n_chunks : n_chunks, vc,
-                         saved + (size_t)(2 * r) * FJD, saved + (size_t)(2 * r + 1) * FJD,
-                         r == g.iters - 1 ? v_out : nullptr, st);
+                         !p32 ? uniform_split(n_chunks) : r == 0 ? uniform_split(plan.n_chunks) : pass_split(g, plan),
+                         vc, saved + (size_t)(2 * r) * FJD, last ? nullptr : saved + (size_t)(2 * r + 1) * FJD,
+                         last ? v_out : nullptr, st);
     SRF_LAUNCH_CHECK("fwd_finish");
   }
   return SRF_OK;
@@ -2354,7 +2391,7 @@ BwdWs bwd_layout(const Geom& g, int n_chunks, void* base) {
     off += srf::align_up(nfloat * sizeof(float), 256);
     return o;
   };
-  const size_t oA = take(F * JD), ogs = take((size_t)g.iters * F * JD), oslab = take((size_t)n_chunks * F * JD),
+  const size_t oA = take(F * JD), ogs = take((size_t)g.iters * F * JD), oslab = take((size_t)legacy_chunks(g, n_chunks) * F * JD),
                ostats = take((size_t)(g.iters - 1) * F * in_n * 2), ogu = take(in_n * (size_t)g.NT() * 16 * Fp),
                oxt = take(in_n * g.din * Fp), owt = take(in_n * JD * g.din);
   size_t op32 = 0, ogl = 0, ogwp = 0;
@@ -2438,7 +2475,7 @@ int bwd_impl(const Geom& g, int n_chunks, const float* emb, const float* W, cons
   const bool p32 = couplings != nullptr && w.p32 != nullptr && R > 1;
   const size_t n_emb = (size_t)g.F() * g.N * g.din;
   // with stored couplings this launch also zeroes g_emb (the gu pass accumulates into it)
-  launch_bwd_finish<D>(g, nullptr, n_chunks, g_v, w.A, saved + (size_t)(2 * (R - 1)) * FJD,
+  launch_bwd_finish<D>(g, nullptr, uniform_split(1), g_v, w.A, saved + (size_t)(2 * (R - 1)) * FJD,
                        w.gs + (size_t)(R - 1) * FJD, st, p32 ? g_emb : nullptr, n_emb, p32 ? w.gumax : nullptr);
   SRF_LAUNCH_CHECK("bwd_finish");
   srf::Fwd32Plan plan{};
@@ -2459,13 +2496,13 @@ int bwd_impl(const Geom& g, int n_chunks, const float* emb, const float* W, cons
                                      couplings + cl.lz + (size_t)(r - 1) * blk,
                                      w.gs + (size_t)r * FJD, stats_r, w.gl + (size_t)(r - 1) * blk * JP, st);
       if (rc) return rc;
-      launch_bwd_finish<D>(g, srf::fwd32_slab(plan, w.p32), plan.n_chunks, nullptr, w.A,
+      launch_bwd_finish<D>(g, srf::fwd32_slab(plan, w.p32), pass_split(g, plan), nullptr, w.A,
                              saved + (size_t)(2 * (r - 1)) * FJD, w.gs + (size_t)(r - 1) * FJD, st);
     } else {
-      dispatch_pass<D, MODE_BWD>(g, pc, n_chunks, emb, W, bias, r, vc, w.gs + (size_t)r * FJD, w.slab, stats_r, 1,
-                                 st);
+      const int lc = legacy_chunks(g, n_chunks);
+      dispatch_pass<D, MODE_BWD>(g, pc, lc, emb, W, bias, r, vc, w.gs + (size_t)r * FJD, w.slab, stats_r, 1, st);
       SRF_LAUNCH_CHECK("route_pass(bwd)");
-      launch_bwd_finish<D>(g, w.slab, n_chunks, nullptr, w.A, saved + (size_t)(2 * (r - 1)) * FJD,
+      launch_bwd_finish<D>(g, w.slab, uniform_split(lc), nullptr, w.A, saved + (size_t)(2 * (r - 1)) * FJD,
                            w.gs + (size_t)(r - 1) * FJD, st);
     }
     SRF_LAUNCH_CHECK("bwd_finish");
@@ -2502,8 +2539,50 @@ int srf_route_dr_set_timing_events(void* const* starts, void* const* stops, int 
 
 int srf_route_dr_auto_chunks(int B, int T, int N, int din, int lpad, int rpad, int J, int dout) {
   Geom g{B, T, N, din, lpad, rpad, J, dout, 1, 0};
-  if (use_fwd32(g)) return srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout).n_chunks;
+  if (use_fwd32(g)) return srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout).plan_arg;
   return auto_chunks(g, pass_cfg(g).NW);
+}
+
+int srf_route_dr_split_table(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks,
+                             int* info, int* table, int capacity) {
+  Geom g{B, T, N, din, lpad, rpad, J, dout, 1, 0};
+  SRF_REQUIRE(B > 0 && T > 0 && N > 0 && lpad >= 0 && rpad >= 0 && use_fwd32(g), "split_table: not a 32x32-pass shape");
+  SRF_REQUIRE(n_chunks == 0 || plan_arg_ok(g, n_chunks), "split_table: bad plan argument %d", n_chunks);
+  SRF_REQUIRE(info != nullptr && capacity >= 0 && (table != nullptr || capacity == 0), "split_table: null argument");
+  const srf::Fwd32Plan p = srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout, n_chunks);
+  const int in_n = g.in_n();
+  const bool bal = p.bal_G > 0;
+  const int n_wg = bal ? p.bal_G : p.n_ftiles * p.n_chunks;
+  info[0] = bal ? 1 : 0;
+  info[1] = n_wg;
+  info[2] = p.n_ftiles * in_n;
+  info[3] = p.n_slots;
+  info[4] = p.plan_arg;
+  int n = 0;
+  auto emit = [&](int w, int ft, int i0, int i1, int slot) {
+    if (n < capacity) {
+      int* row = table + (size_t)n * 5;
+      row[0] = w, row[1] = ft, row[2] = i0, row[3] = i1, row[4] = slot;
+    }
+    ++n;
+  };
+  for (int w = 0; w < n_wg; ++w) {
+    if (!bal) {   // as seg32_at's chunked branch
+      const int ft = w / p.n_chunks, slot = w - ft * p.n_chunks;
+      const int i0 = slot * p.chunk_len;
+      emit(w, ft, std::min(i0, in_n), std::min(in_n, i0 + p.chunk_len), slot);
+      continue;
+    }
+    // as SegWalk / seg32_at walk a span
+    int u = srf::bal_first(w, p.bal_U, p.bal_G);
+    const int u1 = srf::bal_first(w + 1, p.bal_U, p.bal_G);
+    while (u < u1) {
+      const int ft = u / in_n, i0 = u - ft * in_n, i1 = std::min(in_n, i0 + (u1 - u));
+      emit(w, ft, i0, i1, w - srf::bal_owner(ft * in_n, p.bal_U, p.bal_G));
+      u += i1 - i0;
+    }
+  }
+  return n;
 }
 
 size_t srf_route_dr_saved_floats(int B, int T, int J, int dout, int iters) {
@@ -2514,8 +2593,8 @@ size_t srf_route_dr_fwd_workspace(int B, int T, int N, int din, int lpad, int rp
                                   int n_chunks) {
   (void)iters;
   // partial slabs + the i-chunk bias sums of the iteration-0 pass
-  size_t need = (size_t)n_chunks * ((size_t)B * T + 1) * J * dout * sizeof(float);
   Geom g{B, T, N, din, lpad, rpad, J, dout, 1, 0};
+  size_t need = plan_balanced(n_chunks) ? 0 : (size_t)n_chunks * ((size_t)B * T + 1) * J * dout * sizeof(float);
   if (use_fwd32(g))
     need = std::max(need, srf::fwd32_workspace(srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout, n_chunks)));
   return need;
@@ -2548,7 +2627,8 @@ int srf_route_dr_fwd_ex(const float* emb, const float* W, const float* bias, int
   int rc = check_geom(g);
   if (rc) return rc;
   SRF_REQUIRE(emb && W && bias && v_out && saved && workspace, "null pointer argument");
-  SRF_REQUIRE(n_chunks >= 1 && n_chunks <= g.in_n(), "n_chunks %d out of [1, %d]", n_chunks, g.in_n());
+  SRF_REQUIRE(plan_arg_ok(g, n_chunks), "n_chunks %d: neither in [1, %d] nor a balanced plan of the 32x32 passes",
+              n_chunks, g.in_n());
   const size_t need = srf_route_dr_fwd_workspace(B, T, N, din, lpad, rpad, J, dout, iters, n_chunks);
   if (workspace_bytes < need) {
     srf::set_error("forward workspace too small: %zu < %zu", workspace_bytes, need);
@@ -2574,7 +2654,8 @@ int route_dr_bwd_entry(const float* emb, const float* W, const float* bias, int 
   int rc = check_geom(g);
   if (rc) return rc;
   SRF_REQUIRE(emb && W && bias && saved && g_v && g_emb && g_W && g_bias && workspace, "null pointer argument");
-  SRF_REQUIRE(n_chunks >= 1 && n_chunks <= g.in_n(), "n_chunks %d out of [1, %d]", n_chunks, g.in_n());
+  SRF_REQUIRE(plan_arg_ok(g, n_chunks), "n_chunks %d: neither in [1, %d] nor a balanced plan of the 32x32 passes",
+              n_chunks, g.in_n());
   BwdWs w = bwd_layout(g, n_chunks, workspace);
   if (workspace_bytes < w.bytes) {
     srf::set_error("backward workspace too small: %zu < %zu", workspace_bytes, w.bytes);
@@ -2644,7 +2725,8 @@ int srf_route_dr_bwd_weights_ex(const float* emb, int B, int T, int N, int din, 
   int rc = check_geom(g);
   if (rc) return rc;
   SRF_REQUIRE(emb && g_W && g_bias && workspace, "null pointer argument");
-  SRF_REQUIRE(n_chunks >= 1 && n_chunks <= g.in_n(), "n_chunks %d out of [1, %d]", n_chunks, g.in_n());
+  SRF_REQUIRE(plan_arg_ok(g, n_chunks), "n_chunks %d: neither in [1, %d] nor a balanced plan of the 32x32 passes",
+              n_chunks, g.in_n());
   BwdWs w = bwd_layout(g, n_chunks, workspace);
   if (workspace_bytes < w.bytes) {
     srf::set_error("backward workspace too small: %zu < %zu", workspace_bytes, w.bytes);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <cstdint>
 
 namespace srf {
 
@@ -11,19 +12,47 @@ constexpr int kFwd32TW = 4;
 // Frame stride of the stored couplings (frame-minor layout, 32-frame aligned).
 __host__ __device__ inline int fwd32_frame_stride(int F) { return (F + 31) / 32 * 32; }
 
+// Balanced split of the r >= 1 passes.  The linear space of units u = ft * in_n + i
+// (frame tile ft, input capsule i), U = n_ftiles * in_n of them, is cut into G contiguous
+// spans: workgroup w owns [bal_first(w), bal_first(w + 1)).  A segment is the part of a
+// span inside one frame tile; it writes its partial sum into the slab slot that is its
+// ordinal among the tile's segments, w - bal_owner(ft * in_n).  1 <= G <= U (every span
+// holds a unit) and U * (G + 1) < 2^31 (fwd32_plan), so 32-bit arithmetic is exact.
+__host__ __device__ inline int bal_first(int w, int U, int G) {
+  return (int)((uint32_t)w * (uint32_t)U / (uint32_t)G);
+}
+// the workgroup whose span holds unit u: the largest w with bal_first(w) <= u
+__host__ __device__ inline int bal_owner(int u, int U, int G) {
+  return (int)((((uint32_t)u + 1u) * (uint32_t)G - 1u) / (uint32_t)U);
+}
+// segments (= slab slots in use) of frame tile ft
+__host__ __device__ inline int bal_tile_slots(int ft, int in_n, int U, int G) {
+  return bal_owner((ft + 1) * in_n - 1, U, G) - bal_owner(ft * in_n, U, G) + 1;
+}
+// The plan argument `n_chunks` of every entry point selects the split: 0 = the cost
+// model's choice, 1 .. in_n = that many uniform i-chunks, kBalFlag | G = the balanced
+// split over G workgroups (G = 0: as many as are resident).  srf_route_dr_auto_chunks
+// returns the cost model's choice in this encoding, so the forward, the backward and both
+// workspace queries decode the same plan from the same integer.
+constexpr int kBalFlag = 1 << 20;
+
 struct Fwd32Plan {
   int NW;              // waves per workgroup
   int TW;              // 32-row tiles per wave (kFwd32TW; 2 for din 32 with J*dout <= 512)
   int JDp;             // J*dout padded to NW*TW*32 rows
   int xpad;            // zero halves after each x plane (the invalid-frame row)
+  // uniform i-chunks: the iteration-0 pass and its bias sums always, the r >= 1 passes
+  // unless the plan is balanced
   int n_chunks, chunk_len, n_ftiles;
+  int bal_G, bal_U;    // balanced r >= 1 passes: workgroups and units (bal_G = 0: chunked)
+  int n_slots;         // slab slots a frame tile of the r >= 1 passes can use
+  int plan_arg;        // the plan in the entry points' encoding (what auto_chunks returns)
   size_t xplane;       // elements per x plane (data + zero row)
   size_t ws_w, ws_b, ws_x, ws_h, ws_bsum, ws_slab;   // workspace regions (bytes)
 };
 
 bool fwd32_supported(int din, int dout, int J);
-// n_chunks: the input-capsule chunks (workgroups per frame tile) of the routing passes,
-// 0 = the cost model's choice (srf_route_dr_auto_chunks returns it)
+// n_chunks: the plan argument (above)
 Fwd32Plan fwd32_plan(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks = 0);
 // Operand planes (split W, bias, x and their scale header: written by fwd32_prepare,
 // read by every pass)

@@ -54,6 +54,12 @@
 #define SRF_DR_IL 1
 #endif
 
+// SRF_DR_BAL_AUTO (A/B builds only): 0 = the cost model never picks the balanced split of
+// the r >= 1 passes (an explicit plan argument still does).
+#ifndef SRF_DR_BAL_AUTO
+#define SRF_DR_BAL_AUTO 1
+#endif
+
 namespace {
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
@@ -700,6 +706,75 @@ struct Args32 {
   float* cst;
   float* lzst;
   int JP, Fs;
+  // balanced split of the r >= 1 passes (bal_G > 0): workgroup w walks the units
+  // [bal_first(w), bal_first(w + 1)) of bal_U = n_ftiles * in_n (route_fwd32.h)
+  int bal_G, bal_U;
+};
+
+// One segment of a pass workgroup: input capsules [i0, i1) of frame tile ft, partial sum
+// into slab slot `slot`.  Chunked plans give every workgroup one segment (its i-chunk);
+// balanced plans cut the workgroup's span of units u = ft * in_n + i at the tile edges.
+// All four values are wave-uniform and live in SGPRs.
+struct Seg32 {
+  int ft, i0, i1, slot;
+};
+
+// The kernel's arguments (T at byte `off` of the kernarg segment), re-read through a
+// pointer the compiler cannot trace back to them.  What a segment's prologue and epilogue
+// need only once (the Vc / gs / slab pointers, the split's constants) is loaded here by
+// s_load at each segment instead of living in SGPRs across the capsule loop, which has
+// none to spare: held there they were spilled to VGPR lanes, and in the four-row-tile
+// backward pushed vector registers into scratch.
+typedef const __attribute__((address_space(4))) char* kernarg_ptr;
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* kernarg_reload(uint32_t off) {
+  kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return (const __attribute__((address_space(4))) T*)(p + off);
+}
+
+template <class ArgsT>
+__device__ __forceinline__ Seg32 seg32_at(const ArgsT& A, int bid, int u, int u1) {
+  int ft, i0, i1, slot;
+  if (A.bal_G > 0) {
+    ft = (int)((uint32_t)u / (uint32_t)A.in_n);
+    i0 = u - ft * A.in_n;
+    i1 = min(A.in_n, i0 + (u1 - u));
+    slot = bid - srf::bal_owner(ft * A.in_n, A.bal_U, A.bal_G);
+  } else {
+    ft = bid / A.n_chunks;
+    slot = bid - ft * A.n_chunks;
+    i0 = slot * A.chunk_len;
+    i1 = min(A.in_n, i0 + A.chunk_len);
+  }
+  return Seg32{__builtin_amdgcn_readfirstlane(ft), __builtin_amdgcn_readfirstlane(i0),
+               __builtin_amdgcn_readfirstlane(i1), __builtin_amdgcn_readfirstlane(slot)};
+}
+
+// The segment loop of the four pass kernels:
+//   for (SegWalk sw(A);;) { const Seg32 sg = sw.seg(); ...; if (!sw.next(sg)) break; }
+// next() steps to the workgroup's next segment behind a barrier: no stats slot or shared x
+// buffer of the finished segment is still read, and none of its DMAs is still in flight,
+// when the new segment's prologue writes them.
+struct SegWalk {
+  int u;   // the next unit of a balanced span (the one value carried from segment to segment)
+  __device__ __forceinline__ SegWalk(const Args32& A) : u(0) {
+    if (A.bal_G > 0) u = __builtin_amdgcn_readfirstlane(srf::bal_first((int)blockIdx.x, A.bal_U, A.bal_G));
+  }
+  __device__ __forceinline__ Seg32 seg() const {
+    const auto* K = kernarg_reload<Args32>(0);
+    const int bid = blockIdx.x;
+    return seg32_at(*K, bid, u, K->bal_G > 0 ? srf::bal_first(bid + 1, K->bal_U, K->bal_G) : 0);
+  }
+  __device__ __forceinline__ bool next(const Seg32& sg) {
+    const auto* K = kernarg_reload<Args32>(0);
+    if (K->bal_G <= 0) return false;
+    u += sg.i1 - sg.i0;
+    if (u >= __builtin_amdgcn_readfirstlane(srf::bal_first((int)blockIdx.x + 1, K->bal_U, K->bal_G))) return false;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    return true;
+  }
 };
 
 
@@ -1039,7 +1114,8 @@ __global__ __launch_bounds__(64 * 2 * (BN / 32)) void route_fwd32_first_full_ker
   }
 }
 
-// Routing pass r >= 1.  grid: n_ftiles * n_chunks (chunk = blockIdx % n_chunks);
+// Routing pass r >= 1.  grid: n_ftiles * n_chunks (chunk = blockIdx % n_chunks), or the
+// bal_G persistent workgroups of a balanced plan, each walking its segments (SegWalk);
 // block: NW waves of kTW row tiles.  LDS: NW * kTW * 4 KiB of Vc fragments, then
 // 2 x NW x 32 float2 of per-wave softmax stats.
 template <int DIN, int DOUT, int NW, int TW>
@@ -1047,27 +1123,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   constexpr int CP = TW * 32 / DOUT;   // capsule partials per lane
   constexpr int OWN = CP / 2;          // capsules whose logit this lane owns
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int JD = A.J * DOUT;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int wv = threadIdx.x >> 6;
   const int wvu = __builtin_amdgcn_readfirstlane(wv);   // wave index in an SGPR (stats slots)
-  const int r = lane & 31, h = lane >> 5;
-  const int bid = blockIdx.x;
-  const int ft = bid / A.n_chunks, chunk = bid - ft * A.n_chunks;
-  const int f = ft * 32 + r;
-  const int fc = min(f, A.F - 1);
-  const int fb = fc / A.T, ftt = fc - fb * A.T;
-  const bool fvalid = f < A.F;
-  const int i0 = chunk * A.chunk_len, i1 = min(A.in_n, i0 + A.chunk_len);
   const int tbase = __builtin_amdgcn_readfirstlane(wv * TW);
   const int j0 = tbase * 32 / DOUT;
   const Rsrc3 rs{make_rsrc(A.Ws, A.ws_bytes), make_rsrc(A.bs, A.bs_bytes), make_rsrc(A.xs, A.xs_bytes)};
   if (DIN <= 16 && NW > 1 && wv >= NW / 2) __builtin_amdgcn_s_setprio(1);   // din 32: measured faster without
-  const uint32_t wvo = (uint32_t)(((tbase * 32 + r) * DIN + (DIN >= 16 ? 8 * h : 0)) * 2);
-  const uint32_t bvo = (uint32_t)((tbase * 32 + r) * 8);
   const __amdgpu_buffer_rsrc_t crs = make_rsrc(A.cst, A.cst ? (size_t)A.in_n * A.JP * A.Fs * 4 : 0);
   const __amdgpu_buffer_rsrc_t lzs = make_rsrc(A.lzst, A.cst ? (size_t)A.in_n * A.Fs * 4 : 0);
 
-  f4* vcl = reinterpret_cast<f4*>(lds) + (size_t)wv * TW * 4 * 64;
+  f4* vcl = reinterpret_cast<f4*>(lds) + (size_t)tbase * 4 * 64;   // wave's slab, from the SGPR tbase = wv * TW
   float2* st = reinterpret_cast<float2*>(lds + (size_t)NW * TW * 4 * 64 * 4);
   // din 32: each capsule's x fragments DMA'd once per workgroup into LDS (x_dma, two
   // buffers) and read just in time by the pose (pose_prog XJ): no per-wave x loads, and
@@ -1075,8 +1140,28 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   constexpr bool XJ = DIN == 32 && NW > 1;
   __shared__ __attribute__((aligned(16))) char xls[XJ ? 2 * 4 * kXlPiece : 16];
   const char* xs_b = static_cast<const char*>(A.xs);
-  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
   auto xbuf = [&](int c) { return xls + (c & 1) * 4 * kXlPiece; };
+  // the workgroup's segments (one for a chunked plan); everything per tile is set up per
+  // segment (loop body not indented)
+  for (SegWalk sw(A);;) {
+  const Seg32 sg = sw.seg();
+  const int ft = sg.ft, i0 = sg.i0, i1 = sg.i1;
+  // the lane id and what derives from it, re-derived per segment (asm: not hoisted): as
+  // loop invariants of the segment loop the row offsets and operand offsets were held in
+  // VGPRs across the capsule loop, which at four row tiles has none to spare
+  const int lane = lane_asm(), r = lane & 31, h = lane >> 5;
+  const uint32_t wvo = (uint32_t)(((tbase * 32 + r) * DIN + (DIN >= 16 ? 8 * h : 0)) * 2);
+  const uint32_t bvo = (uint32_t)((tbase * 32 + r) * 8);
+  // re-read per segment, and again for the write-out: the row < JD lane masks derived from
+  // a value held across the segments were hoisted out of the loop, two SGPRs per mask
+  // (and the reciprocal of T, of the per-lane division below, in a VGPR)
+  const int JD = kernarg_reload<Args32>(0)->J * DOUT;
+  const int Tk = kernarg_reload<Args32>(0)->T;
+  const int f = ft * 32 + r;
+  const int fc = min(f, A.F - 1);
+  const int fb = fc / Tk, ftt = fc - fb * Tk;
+  const bool fvalid = f < A.F;
+  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
   // Vc rows of this wave's tiles -> private LDS in fragment order
 #pragma unroll
   for (int t = 0; t < TW; ++t)
@@ -1084,7 +1169,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
     for (int q = 0; q < 4; ++q) {
       const int row = (tbase + t) * 32 + 8 * q + 4 * h;
       f4 v = {0.f, 0.f, 0.f, 0.f};
-      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(A.vc + (size_t)f * JD + row);
+      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(kernarg_reload<Args32>(0)->vc + (size_t)f * JD + row);
       vcl[(t * 4 + q) * 64 + lane] = v;
     }
   // owned-capsule masks: 0 or -inf added to the logit
@@ -1268,16 +1353,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         }
     }
   }
+  {
+    // the write-out's lane offsets from a lane id of its own: shared with the prologue's
+    // they stay live across the capsule loop (an asm result is not rematerialised)
+    const auto* K = kernarg_reload<Args32>(0);
+    const int JD = K->J * DOUT;
+    const int le = lane_asm(), fe = ft * 32 + (le & 31), he = le >> 5;
+    float* const sl = K->slab + (size_t)sg.slot * A.F * JD;   // the segment's slab slot
 #pragma unroll
-  for (int t = 0; t < TW; ++t)
+    for (int t = 0; t < TW; ++t)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = (tbase + t) * 32 + 8 * q + 4 * h;
-      if (fvalid && row < JD) {
-        f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
-        *reinterpret_cast<f4*>(A.slab + ((size_t)chunk * A.F + f) * JD + row) = v * inv;
+      for (int q = 0; q < 4; ++q) {
+        const int row = (tbase + t) * 32 + 8 * q + 4 * he;
+        if (fe < A.F && row < JD) {
+          f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
+          *reinterpret_cast<f4*>(sl + (size_t)fe * JD + row) = v * inv;
+        }
       }
-    }
+  }
+  if (!sw.next(sg)) break;
+  }
 }
 
 
@@ -1293,16 +1388,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   constexpr int OWN = CP / 2;          // capsules whose logit this lane owns
   static_assert(NW > 1, "the pipelined pass exchanges softmax stats between waves");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int JD = A.J * DOUT;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const int bid = blockIdx.x;
-  const int ft = bid / A.n_chunks, chunk = bid - ft * A.n_chunks;
-  const int f = ft * 32 + r;
-  const int fc = min(f, A.F - 1);
-  const int fb = fc / A.T, ftt = fc - fb * A.T;
-  const bool fvalid = f < A.F;
-  const int i0 = chunk * A.chunk_len, i1 = min(A.in_n, i0 + A.chunk_len);
   const int tbase = __builtin_amdgcn_readfirstlane(wv * TW);
   const int j0 = tbase * 32 / DOUT;
   const Rsrc3 rs{make_rsrc(A.Ws, A.ws_bytes), make_rsrc(A.bs, A.bs_bytes), make_rsrc(A.xs, A.xs_bytes)};
@@ -1319,15 +1406,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   __shared__ __attribute__((aligned(16))) char xls[XL ? 2 * 4 * kXlPiece : 16];
   char* xb = xls;
   const char* xs_b = static_cast<const char*>(A.xs);
-  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
   auto xbuf = [&](int c) { return xb + (c & 1) * 4 * kXlPiece; };
+  // the workgroup's segments, as route_fwd32_kernel (loop body not indented)
+  for (SegWalk sw(A);;) {
+  const Seg32 sg = sw.seg();
+  const int ft = sg.ft, i0 = sg.i0, i1 = sg.i1;
+  // re-read per segment, and again for the write-out: the row < JD lane masks derived from
+  // a value held across the segments were hoisted out of the loop, two SGPRs per mask
+  const int JD = kernarg_reload<Args32>(0)->J * DOUT;
+  const int f = ft * 32 + r;
+  const int fc = min(f, A.F - 1);
+  const int fb = fc / A.T, ftt = fc - fb * A.T;
+  const bool fvalid = f < A.F;
+  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
 #pragma unroll
   for (int t = 0; t < TW; ++t)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int row = (tbase + t) * 32 + 8 * q + 4 * h;
       f4 v = {0.f, 0.f, 0.f, 0.f};
-      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(A.vc + (size_t)f * JD + row);
+      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(kernarg_reload<Args32>(0)->vc + (size_t)f * JD + row);
       vcr[t][q] = v;
     }
   float mk[OWN];
@@ -1547,16 +1645,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
     }
     if constexpr (XL) xl_wait();   // no DMA into LDS outlives the workgroup
   }
+  {
+    // the write-out's lane offsets from a lane id of its own: shared with the prologue's
+    // they stay live across the capsule loop (an asm result is not rematerialised)
+    const auto* K = kernarg_reload<Args32>(0);
+    const int JD = K->J * DOUT;
+    const int le = lane_asm(), fe = ft * 32 + (le & 31), he = le >> 5;
+    float* const sl = K->slab + (size_t)sg.slot * A.F * JD;   // the segment's slab slot
 #pragma unroll
-  for (int t = 0; t < TW; ++t)
+    for (int t = 0; t < TW; ++t)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = (tbase + t) * 32 + 8 * q + 4 * h;
-      if (fvalid && row < JD) {
-        f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
-        *reinterpret_cast<f4*>(A.slab + ((size_t)chunk * A.F + f) * JD + row) = v * inv;
+      for (int q = 0; q < 4; ++q) {
+        const int row = (tbase + t) * 32 + 8 * q + 4 * he;
+        if (fe < A.F && row < JD) {
+          f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
+          *reinterpret_cast<f4*>(sl + (size_t)fe * JD + row) = v * inv;
+        }
       }
-    }
+  }
+  if (!sw.next(sg)) break;
+  }
 }
 
 // ------------------------------------------------------------------ backward pass
@@ -1589,43 +1697,51 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   constexpr int CP = TW * 32 / DOUT;
   constexpr int OWN = CP / 2;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int JD = A.J * DOUT;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int wv = threadIdx.x >> 6;
   const int wvu = __builtin_amdgcn_readfirstlane(wv);   // wave index in an SGPR (stats slots)
-  const int r = lane & 31, h = lane >> 5;
-  const int bid = blockIdx.x;
-  const int ft = bid / A.n_chunks, chunk = bid - ft * A.n_chunks;
-  const int f = ft * 32 + r;
-  const int fc = min(f, A.F - 1);
-  const int fb = fc / A.T, ftt = fc - fb * A.T;
-  const bool fvalid = f < A.F;
-  const int i0 = chunk * A.chunk_len, i1 = min(A.in_n, i0 + A.chunk_len);
   const int tbase = __builtin_amdgcn_readfirstlane(wv * TW);
   const int j0 = tbase * 32 / DOUT;
   const Rsrc3 rs{make_rsrc(A.Ws, A.ws_bytes), make_rsrc(A.bs, A.bs_bytes), make_rsrc(A.xs, A.xs_bytes)};
   if (DIN <= 16 && NW > 1 && wv >= NW / 2) __builtin_amdgcn_s_setprio(1);   // din 32: measured faster without
-  const uint32_t wvo = (uint32_t)(((tbase * 32 + r) * DIN + (DIN >= 16 ? 8 * h : 0)) * 2);
-  const uint32_t bvo = (uint32_t)((tbase * 32 + r) * 8);
   // logZ^r through a buffer descriptor: a 32-bit lane offset instead of a 64-bit
   // pointer held across the capsule loop (which spilled, its reload's vmcnt(0) draining
   // the operand prefetch)
   const __amdgpu_buffer_rsrc_t lzr = make_rsrc(Bk.lz, (size_t)A.in_n * A.Fs * 4);
 
-  f4* gsl = reinterpret_cast<f4*>(lds) + (size_t)wv * TW * 4 * 64;
+  f4* gsl = reinterpret_cast<f4*>(lds) + (size_t)tbase * 4 * 64;   // wave's slab, from the SGPR tbase = wv * TW
   float* st = lds + (size_t)NW * TW * 4 * 64 * 4;
   // din 32: shared x fragments read just in time, as route_fwd32_kernel
   constexpr bool XJ = DIN == 32 && NW > 1;
   __shared__ __attribute__((aligned(16))) char xls[XJ ? 2 * 4 * kXlPiece : 16];
   const char* xs_b = static_cast<const char*>(A.xs);
-  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
   auto xbuf = [&](int c) { return xls + (c & 1) * 4 * kXlPiece; };
+  // the workgroup's segments, as route_fwd32_kernel (loop body not indented)
+  for (SegWalk sw(A);;) {
+  const Seg32 sg = sw.seg();
+  const int ft = sg.ft, i0 = sg.i0, i1 = sg.i1;
+  // the lane id and what derives from it, re-derived per segment (asm: not hoisted): as
+  // loop invariants of the segment loop the row offsets and operand offsets were held in
+  // VGPRs across the capsule loop, which at four row tiles has none to spare
+  const int lane = lane_asm(), r = lane & 31, h = lane >> 5;
+  const uint32_t wvo = (uint32_t)(((tbase * 32 + r) * DIN + (DIN >= 16 ? 8 * h : 0)) * 2);
+  const uint32_t bvo = (uint32_t)((tbase * 32 + r) * 8);
+  // re-read per segment, and again for the write-out: the row < JD lane masks derived from
+  // a value held across the segments were hoisted out of the loop, two SGPRs per mask
+  // (and the reciprocal of T, of the per-lane division below, in a VGPR)
+  const int JD = kernarg_reload<Args32>(0)->J * DOUT;
+  const int Tk = kernarg_reload<Args32>(0)->T;
+  const int f = ft * 32 + r;
+  const int fc = min(f, A.F - 1);
+  const int fb = fc / Tk, ftt = fc - fb * Tk;
+  const bool fvalid = f < A.F;
+  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
 #pragma unroll
   for (int t = 0; t < TW; ++t)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int row = (tbase + t) * 32 + 8 * q + 4 * h;
       f4 v = {0.f, 0.f, 0.f, 0.f};
-      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(Bk.gs + (size_t)f * JD + row);
+      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(kernarg_reload<Bwd32Args>(sizeof(Args32))->gs + (size_t)f * JD + row);
       gsl[(t * 4 + q) * 64 + lane] = v;
     }
   const bf8 ones = ones_frag(h);
@@ -1788,16 +1904,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         }
     }
   }
+  {
+    // the write-out's lane offsets from a lane id of its own: shared with the prologue's
+    // they stay live across the capsule loop (an asm result is not rematerialised)
+    const auto* K = kernarg_reload<Args32>(0);
+    const int JD = K->J * DOUT;
+    const int le = lane_asm(), fe = ft * 32 + (le & 31), he = le >> 5;
+    float* const sl = K->slab + (size_t)sg.slot * A.F * JD;   // the segment's slab slot
 #pragma unroll
-  for (int t = 0; t < TW; ++t)
+    for (int t = 0; t < TW; ++t)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = (tbase + t) * 32 + 8 * q + 4 * h;
-      if (fvalid && row < JD) {
-        f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
-        *reinterpret_cast<f4*>(A.slab + ((size_t)chunk * A.F + f) * JD + row) = v * inv;
+      for (int q = 0; q < 4; ++q) {
+        const int row = (tbase + t) * 32 + 8 * q + 4 * he;
+        if (fe < A.F && row < JD) {
+          f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
+          *reinterpret_cast<f4*>(sl + (size_t)fe * JD + row) = v * inv;
+        }
       }
-    }
+  }
+  if (!sw.next(sg)) break;
+  }
 }
 
 
@@ -1811,16 +1937,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   constexpr int OWN = CP / 2;
   static_assert(NW > 1, "the pipelined pass exchanges sigma partials between waves");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int JD = A.J * DOUT;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
-  const int bid = blockIdx.x;
-  const int ft = bid / A.n_chunks, chunk = bid - ft * A.n_chunks;
-  const int f = ft * 32 + r;
-  const int fc = min(f, A.F - 1);
-  const int fb = fc / A.T, ftt = fc - fb * A.T;
-  const bool fvalid = f < A.F;
-  const int i0 = chunk * A.chunk_len, i1 = min(A.in_n, i0 + A.chunk_len);
   const int tbase = __builtin_amdgcn_readfirstlane(wv * TW);
   const int j0 = tbase * 32 / DOUT;
   const Rsrc3 rs{make_rsrc(A.Ws, A.ws_bytes), make_rsrc(A.bs, A.bs_bytes), make_rsrc(A.xs, A.xs_bytes)};
@@ -1834,15 +1952,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   __shared__ __attribute__((aligned(16))) char xls[XL ? 2 * 4 * kXlPiece : 16];
   char* xb = xls;
   const char* xs_b = static_cast<const char*>(A.xs);
-  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
   auto xbuf = [&](int c) { return xb + (c & 1) * 4 * kXlPiece; };
+  // the workgroup's segments, as route_fwd32_kernel (loop body not indented)
+  for (SegWalk sw(A);;) {
+  const Seg32 sg = sw.seg();
+  const int ft = sg.ft, i0 = sg.i0, i1 = sg.i1;
+  // re-read per segment, and again for the write-out: the row < JD lane masks derived from
+  // a value held across the segments were hoisted out of the loop, two SGPRs per mask
+  const int JD = kernarg_reload<Args32>(0)->J * DOUT;
+  const int f = ft * 32 + r;
+  const int fc = min(f, A.F - 1);
+  const int fb = fc / A.T, ftt = fc - fb * A.T;
+  const bool fvalid = f < A.F;
+  auto xsrc = [&](int c) { return x_voff<DIN>(min(c, i1 - 1), A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off); };
 #pragma unroll
   for (int t = 0; t < TW; ++t)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int row = (tbase + t) * 32 + 8 * q + 4 * h;
       f4 v = {0.f, 0.f, 0.f, 0.f};
-      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(Bk.gs + (size_t)f * JD + row);
+      if (fvalid && row < JD) v = *reinterpret_cast<const f4*>(kernarg_reload<Bwd32Args>(sizeof(Args32))->gs + (size_t)f * JD + row);
       gsl[(t * 4 + q) * 64 + lane] = v;
     }
   const bf8 ones = ones_frag(h);
@@ -2050,16 +2179,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
     }
     if constexpr (XL) xl_wait();   // no DMA into LDS outlives the workgroup
   }
+  {
+    // the write-out's lane offsets from a lane id of its own: shared with the prologue's
+    // they stay live across the capsule loop (an asm result is not rematerialised)
+    const auto* K = kernarg_reload<Args32>(0);
+    const int JD = K->J * DOUT;
+    const int le = lane_asm(), fe = ft * 32 + (le & 31), he = le >> 5;
+    float* const sl = K->slab + (size_t)sg.slot * A.F * JD;   // the segment's slab slot
 #pragma unroll
-  for (int t = 0; t < TW; ++t)
+    for (int t = 0; t < TW; ++t)
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = (tbase + t) * 32 + 8 * q + 4 * h;
-      if (fvalid && row < JD) {
-        f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
-        *reinterpret_cast<f4*>(A.slab + ((size_t)chunk * A.F + f) * JD + row) = v * inv;
+      for (int q = 0; q < 4; ++q) {
+        const int row = (tbase + t) * 32 + 8 * q + 4 * he;
+        if (fe < A.F && row < JD) {
+          f4 v = {acc[t][4 * q], acc[t][4 * q + 1], acc[t][4 * q + 2], acc[t][4 * q + 3]};
+          *reinterpret_cast<f4*>(sl + (size_t)fe * JD + row) = v * inv;
+        }
       }
-    }
+  }
+  if (!sw.next(sg)) break;
+  }
 }
 
 }  // namespace
@@ -2093,17 +2232,39 @@ Fwd32Plan fwd32_plan(int B, int T, int N, int din, int lpad, int rpad, int J, in
   p.xpad = din == 32 ? 32 : 16;
   const int F = B * T;
   const int n_ftiles = (F + 31) / 32;
-  // NW > 1: as many workgroups per CU as the waves (2 per SIMD) and the LDS (Vc
-  // slabs) allow; single-wave workgroups: up to 4 per CU.
+  // How the capsule iterations of a pass are spread over the CUs.  A pass has
+  // U = n_ftiles * in_n units of work (one input capsule of one 32-frame tile) and `slots`
+  // resident workgroups -- NW > 1: as many per CU as the waves (2 per SIMD) and the LDS (Vc
+  // slabs) allow; single-wave workgroups: up to 4 per CU.  The cost model charges a
+  // workgroup one per capsule iteration and kSegCost per segment it opens (prologue: Vc
+  // load, pipeline fill, first barrier; epilogue: slab write-out), times 1 + 0.002 per slab
+  // the finish has to sum.
+  //   chunked, c chunks:  n_ftiles * c workgroups of ceil(in_n / c) capsules run in
+  //                       ceil(n_ftiles * c / slots) rounds: rounds * (len + kSegCost).
+  //                       The last round is rarely full (C4: 700 workgroups on 256 slots,
+  //                       3 rounds x 23 = 69 against a floor of 54.7 iterations per CU).
+  //   balanced, G spans:  G = min(slots, U) persistent workgroups of ceil(U / G) units,
+  //                       each cut at the tile edges it crosses: one round of
+  //                       ceil(U / G) + kSegCost * segments (C4: 55 + 2 x 3 = 61).
+  // The cheaper one is the plan, but balanced only where the GPU confirmed it:
+  // din 32 with two row tiles per wave, the C3 / C4 inner layers (C4 step -1.3 %).  With
+  // four row tiles (layer 6) it measured 20-40 % slower per pass, as did the model's
+  // promise of -12 % per pass everywhere: it counts iterations, not where W comes from
+  // (uniform chunks walk the same capsules in step on an XCD, so W is reused in its L2;
+  // balanced spans start at G different capsules).  An explicit plan argument
+  // overrides the model: 1 .. in_n forces that chunk count, kBalFlag | G the balanced split.
+  // The iteration-0 pass and the bias sums keep the best chunk count in either case.
+  constexpr int kSegCost = 3;
   const int per_cu = std::max(1, std::min(8 / p.NW, (int)(160 * 1024 / fwd32_lds(p))));
   const int slots = p.NW > 1 ? 256 * per_cu : 1024;
   int best = 1;
   double best_cost = 1e30;
-  const int forced = n_chunks;
+  const bool force_bal = n_chunks > 0 && (n_chunks & kBalFlag) != 0;
+  const int forced = force_bal ? 0 : n_chunks;
   for (int c = 1; c <= std::min(in_n, 96); ++c) {
     const int rounds = (n_ftiles * c + slots - 1) / slots;
     const int len = (in_n + c - 1) / c;
-    double cost = (double)rounds * (len + 3) * (1.0 + 0.002 * c);
+    double cost = (double)rounds * (len + kSegCost) * (1.0 + 0.002 * c);
     if (forced > 0) cost = (c == std::min(forced, in_n)) ? 0.0 : 1.0;
     if (cost < best_cost) {
       best_cost = cost;
@@ -2113,13 +2274,38 @@ Fwd32Plan fwd32_plan(int B, int T, int N, int din, int lpad, int rpad, int J, in
   p.n_chunks = best;
   p.chunk_len = (in_n + best - 1) / best;
   p.n_ftiles = n_ftiles;
+  p.bal_G = 0;
+  p.bal_U = 0;
+  p.n_slots = best;
+  p.plan_arg = best;
+  {
+    const long long U = (long long)n_ftiles * in_n;
+    long long G = force_bal ? (n_chunks & (kBalFlag - 1)) : 0;
+    if (G <= 0) G = slots;
+    G = std::min(G, U);
+    const bool fits = U * (G + 1) < (1ll << 31);   // bal_first / bal_owner in 32 bits
+    if (fits && forced <= 0) {
+      const int len = (int)((U + G - 1) / G);
+      const int segs = (len - 1 + in_n - 1) / in_n + 1;   // tiles a span of len units can touch
+      int n_slots = 1;
+      for (int ft = 0; ft < n_ftiles; ++ft) n_slots = std::max(n_slots, bal_tile_slots(ft, in_n, (int)U, (int)G));
+      const double cost = (double)(len + kSegCost * segs) * (1.0 + 0.002 * n_slots);
+      if (force_bal || (SRF_DR_BAL_AUTO && din == 32 && p.NW > 1 && p.TW == 2 && cost < best_cost)) {
+        p.bal_G = (int)G;
+        p.bal_U = (int)U;
+        p.n_slots = n_slots;
+        p.plan_arg = kBalFlag | (int)G;
+      }
+    }
+  }
   p.xplane = (size_t)F * N * din + p.xpad;
   p.ws_w = srf::align_up((size_t)2 * in_n * p.JDp * din * 2, 256);
   p.ws_b = srf::align_up((size_t)in_n * p.JDp * 4 * 2, 256);
   p.ws_x = srf::align_up((size_t)2 * p.xplane * 2, 256);
   p.ws_h = (size_t)(2 * kAbsBlocks + 64) * 4;   // header + absmax block maxima
   p.ws_bsum = srf::align_up((size_t)best * JD * 4, 256);
-  p.ws_slab = srf::align_up((size_t)best * F * JD * 4, 256);
+  // the slabs of the iteration-0 pass (best) or of a later pass (n_slots), whichever are more
+  p.ws_slab = srf::align_up((size_t)std::max(best, p.n_slots) * F * JD * 4, 256);
   return p;
 }
 
@@ -2197,7 +2383,7 @@ static int launch_rpass(const Fwd32Plan& p, const Args32& a, hipStream_t st) {
                                                     : route_fwd32_kernel<DIN, DOUT, NW, TW>;
   if (lds > 64 * 1024)
     SRF_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(p.n_ftiles * p.n_chunks), dim3(64 * NW), lds, st, a);
+  hipLaunchKernelGGL(kern, dim3(p.bal_G > 0 ? p.bal_G : p.n_ftiles * p.n_chunks), dim3(64 * NW), lds, st, a);
   SRF_LAUNCH_CHECK("route_fwd32");
   return SRF_OK;
 }
@@ -2267,6 +2453,8 @@ static Args32 make_args32(const Fwd32Plan& p, const void* planes, void* scratch,
   a.lzst = nullptr;
   a.JP = p.JDp / dout;
   a.Fs = fwd32_frame_stride(B * T);
+  a.bal_G = p.bal_G;
+  a.bal_U = p.bal_U;
   return a;
 }
 
@@ -2365,7 +2553,7 @@ static int launch_bpass(const Fwd32Plan& p, const Args32& a, const Bwd32Args& b,
                                                     : route_bwd32_kernel<DIN, DOUT, NW, TW>;
   if (lds > 64 * 1024)
     SRF_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(p.n_ftiles * p.n_chunks), dim3(64 * NW), lds, st, a, b);
+  hipLaunchKernelGGL(kern, dim3(p.bal_G > 0 ? p.bal_G : p.n_ftiles * p.n_chunks), dim3(64 * NW), lds, st, a, b);
   SRF_LAUNCH_CHECK("route_bwd32");
   return SRF_OK;
 }
