@@ -849,8 +849,11 @@ __global__ __launch_bounds__(256, DIN >= 32 ? (R >= 4 ? 2 : 3) : (R >= 4 ? 3 : 4
 // gu pass from stored couplings on 32x32x16 split-fp16 MFMA (din 32, dout 32: the
 // C3 / C4 DR layers).  gx^T[e][f] = sum_row W^T[e][row] gu[row][f] with
 //   * W' = 2^aw W (the forward's exponent, prep header hdr[1]) and gu' = 2^eg gu, eg
-//     one exponent per (wave, capsule, frame) from the frame's max |gu| over the
-//     wave's 32 rows, so max|W'|, max|gu'| < 2^14;
+//     one exponent per (wave, capsule, frame) from a bound on the frame's max |gu| over
+//     the wave's 32 rows: the sum of the terms' maxima, |c^r| max|gs^r| and
+//     |gL^r| max|Vc^r| (the row maxima reduced once per output-capsule group), which is
+//     known before gu is formed and at most log2(2R - 1) bits above the true maximum;
+//     so max|W'|, max|gu'| < 2^14;
 //   * a' = a1 + a2 (fp16 each) and the tile W1 gu1 + W1 gu2 + W2 gu1 (the dropped
 //     W2 gu2 <= 2^-22 |W' gu'|), three MFMAs per 16-row K step, products exact in fp32;
 //   * the result scaled back by the exact 2^-(aw+eg) of the lane's frame column.
@@ -879,8 +882,23 @@ __device__ __forceinline__ f16v mfma32h(const h8& a, const h8& b, const f16v& c)
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
-// The lane max of |gu| also goes to *gumax (one atomic max per wave; the caller zeroes
-// it): route_gw16s_kernel takes its per-layer exponent from it.
+// Split by masking, four pairs -> the 8 halves of an MFMA operand: hi = a' with the low
+// 13 mantissa bits cleared (exact in fp16 in the normal range), lo = f16(a' - hi);
+// packed conversions.
+__device__ __forceinline__ void split8h(const f2 (&a)[4], h8& hi, h8& lo) {
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    const f2 hf = __builtin_bit_cast(f2, __builtin_bit_cast(u2, a[v]) & 0xFFFFE000u);
+    const h2 ph = __builtin_convertvector(hf, h2), pl = __builtin_convertvector(a[v] - hf, h2);
+    hi[2 * v] = ph[0];
+    hi[2 * v + 1] = ph[1];
+    lo[2 * v] = pl[0];
+    lo[2 * v + 1] = pl[1];
+  }
+}
+
+// The lane max of that bound also goes to *gumax (one atomic max per wave; the caller
+// zeroes it): route_gw16s_kernel takes its per-layer exponent from it.
 template <int R>
 __global__ __launch_bounds__(64 * kGux16NW, kGux16Occ) void route_gux16_kernel(
     const float* __restrict__ WT, const float* __restrict__ hdr, int F, int T, int N, int lpad, int in_n, int J,
@@ -958,8 +976,27 @@ __global__ __launch_bounds__(64 * kGux16NW, kGux16Occ) void route_gux16_kernel(
       rows(gs + (size_t)r * FJD, gsr[r]);
       if (r > 0) rows(saved + (size_t)(2 * (r - 1) + 1) * FJD, vcr[r - 1]);
     }
+  }
+  // the frame's maxima over the wave's 32 rows, gm[r] = max |gs^r| (c^0 folded into gm[0])
+  // and vm[r] = max |Vc^(r+1)|: a capsule's max |gu| is at most
+  //   gm[0] + sum_r (|c^r| gm[r] + |gL^r| vm[r-1]),
+  // known before its gu is formed
+  float gm[R], vm[RV];
+  {
+    auto rowmax = [&](const float (&o)[16]) {
+      float m = 0.f;
 #pragma unroll
-    for (int k = 0; k < 16; ++k) gsr[0][k] *= c0;
+      for (int k = 0; k < 16; k += 2) m = fmaxf(m, fmaxf(fabsf(o[k]), fabsf(o[k + 1])));
+      float ma, mb;
+      xpair32(m, ma, mb);
+      return fmaxf(ma, mb);
+    };
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      gm[r] = rowmax(gsr[r]);
+      if (r > 0) vm[r - 1] = rowmax(vcr[r - 1]);
+    }
+    gm[0] *= c0;
   }
   const int aw = (int)hdr[1];
   // split W^T planes (prep32_kernel, wt16) [i][tile][h][e][8 rows] hi, then lo: K step
@@ -1000,37 +1037,37 @@ __global__ __launch_bounds__(64 * kGux16NW, kGux16Occ) void route_gux16_kernel(
   };
   auto compute = [&](auto slot) {
     constexpr int sl = decltype(slot)::value;
-    // gu on packed pairs (v_pk_fma_f32), the lane's max |gu| for the frame's exponent
-    f2 gu[8];
-    float m = 0.f;
+    // the exponent from the bound, folded into the coefficients: the packed fma chain
+    // (v_pk_fma_f32) gives gu' = 2^eg gu directly and the split waits on no reduction
+    float mh = gm[0];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      f2 a = f2{gsr[0][2 * k], gsr[0][2 * k + 1]};
-#pragma unroll
-      for (int r = 0; r < RV; ++r) {
-        a = __builtin_elementwise_fma(f2{c_b[sl][r], c_b[sl][r]}, f2{gsr[r + 1][2 * k], gsr[r + 1][2 * k + 1]}, a);
-        a = __builtin_elementwise_fma(f2{g_b[sl][r], g_b[sl][r]}, f2{vcr[r][2 * k], vcr[r][2 * k + 1]}, a);
-      }
-      gu[k] = a;
-      m = fmaxf(m, fmaxf(fabsf(a[0]), fabsf(a[1])));
-    }
-    gmax = fmaxf(gmax, m);
-    float ma, mb;
-    xpair32(m, ma, mb);
-    const int eg = srf_split_exp(fmaxf(ma, mb));
+    for (int r = 0; r < RV; ++r) mh = fmaf(fabsf(g_b[sl][r]), vm[r], fmaf(fabsf(c_b[sl][r]), gm[r + 1], mh));
+    gmax = fmaxf(gmax, mh);
+    const int eg = srf_split_exp(mh);
     const float sg = srf_exp2i(eg);
-    // split by masking: hi = gu' with the low 13 mantissa bits cleared (exact in fp16),
-    // lo = f16(gu' - hi); packed conversions
+    const float s0 = c0 * sg;
+    float cs[RV], gl[RV];
+#pragma unroll
+    for (int r = 0; r < RV; ++r) {
+      cs[r] = c_b[sl][r] * sg;
+      gl[r] = g_b[sl][r] * sg;
+    }
     h8 bh[2], bl[2];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const f2 a = gu[k] * sg;
-      const f2 hi = __builtin_bit_cast(f2, __builtin_bit_cast(u2, a) & 0xFFFFE000u);
-      const h2 ph = __builtin_convertvector(hi, h2), pl = __builtin_convertvector(a - hi, h2);
-      bh[k >> 2][2 * (k & 3)] = ph[0];
-      bh[k >> 2][2 * (k & 3) + 1] = ph[1];
-      bl[k >> 2][2 * (k & 3)] = pl[0];
-      bl[k >> 2][2 * (k & 3) + 1] = pl[1];
+    for (int ks = 0; ks < 2; ++ks) {
+      f2 gu[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int k = 4 * ks + v;
+        f2 a = f2{gsr[0][2 * k], gsr[0][2 * k + 1]} * s0;
+#pragma unroll
+        for (int r = 0; r < RV; ++r) {
+          a = __builtin_elementwise_fma(f2{cs[r], cs[r]}, f2{gsr[r + 1][2 * k], gsr[r + 1][2 * k + 1]}, a);
+          a = __builtin_elementwise_fma(f2{gl[r], gl[r]}, f2{vcr[r][2 * k], vcr[r][2 * k + 1]}, a);
+        }
+        gu[v] = a;
+      }
+      split8h(gu, bh[ks], bl[ks]);
     }
     f16v acc = {};
 #pragma unroll
@@ -1595,8 +1632,9 @@ __global__ __launch_bounds__(256, (D >= 32 && CAP >= 8) ? 2 : 3) void route_gw3_
 // couplings: the C3 / C4 DR layers): gW^T_i[e][row] = sum_f x_i^T[e][f] gu_i[f][row].
 //   * x' = 2^bx x (the forward's exponent, hdr[2]), split by the forward's prep into
 //     fp16 hi / lo planes blocked per 16 frames (xt16: [i][f/16][hi|lo][e][16]);
-//   * gu' = 2^eg gu with ONE exponent for the layer, from max|gu| that the gx pass
-//     (route_gux16_kernel) leaves in *gumax, so max|gu'| < 2^14; split into fp16
+//   * gu' = 2^eg gu with ONE exponent for the layer, from the bound on max|gu| that the
+//     gx pass (route_gux16_kernel) leaves in *gumax, so max|gu'| < 2^14; 2^eg rides on
+//     the couplings (scaled as they are staged to LDS) and on c^0; split into fp16
 //     hi / lo by masking: hi = gu' with its low 13 mantissa bits cleared (exact in
 //     fp16 in the normal range), lo = f16(gu' - hi).  Products of one exponent pair
 //     sum straight into the fp32 accumulator: three MFMAs per capsule and 16-frame K
@@ -1667,11 +1705,13 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
   constexpr int NCPL = CAP * CG / 4;
   const char* src[NQ];
   int dst[NQ];
-  int step[NQ];
+  bool cpl[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
     const int idx = min(q * 256 + (int)threadIdx.x, CAP * PQ - 1);
-    if (idx < NCPL) {
+    // known at compile time wherever a round of 256 pieces is all couplings or all x
+    cpl[q] = (q + 1) * 256 <= NCPL || (q * 256 < NCPL && idx < NCPL);
+    if (cpl[q]) {
       const int k = idx / (CG / 4), rem = idx - k * (CG / 4);
       const int i = i0 + min(k, ncap - 1);
       const int fq = rem & 3, jq = (rem >> 2) & 3, cg = rem >> 4;   // cg = r * 2 + (0: c, 1: gL)
@@ -1679,27 +1719,26 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
       src[q] = reinterpret_cast<const char*>(((cg & 1) ? glst : cst) + (size_t)(cg >> 1) * cblk +
                                              ((size_t)i * JP + jj) * Fs + 4 * fq);
       dst[q] = k * PCB + rem * 16;
-      step[q] = 64;
     } else {
       const int x = idx - NCPL, k = x >> 7, xr = x & 127;
       const int p = xr >> 6, e = (xr >> 1) & 31, hf = xr & 1;
       const int i = i0 + min(k, ncap - 1);
       src[q] = reinterpret_cast<const char*>(x16 + (((size_t)i * NFT * 2 + p) * 32 + e) * 16 + hf * 8);
       dst[q] = k * PCB + CG * 4 + p * (D * 16 * 2) + (e * 16 + ((hf ^ ((e >> 3) & 1)) * 8)) * 2;
-      step[q] = 2 * 32 * 16 * 2;
     }
   }
   f4 sv[NQ];
   auto stage_load = [&](int ft) {
 #pragma unroll
-    for (int q = 0; q < NQ; ++q) sv[q] = *reinterpret_cast<const f4*>(src[q] + (size_t)ft * step[q]);
+    for (int q = 0; q < NQ; ++q) sv[q] = *reinterpret_cast<const f4*>(src[q] + (size_t)ft * (cpl[q] ? 64 : 2 * 32 * 16 * 2));
   };
   auto stage_store = [&](int buf) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int idx = q * 256 + threadIdx.x;
       if ((CAP * PQ) % 256 != 0 && idx >= CAP * PQ) continue;
-      *reinterpret_cast<f4*>(&stg[buf][dst[q]]) = sv[q];
+      // couplings go to LDS as c 2^eg, gL 2^eg (exact): the tile loop then scales no vector
+      *reinterpret_cast<f4*>(&stg[buf][dst[q]]) = cpl[q] ? sv[q] * sg : sv[q];
     }
   };
   // per-frame vectors of the lane's row, frames 8h + 0..7 of a tile: buffer loads, 0 past F
@@ -1713,10 +1752,11 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
                                                       (int)nrec, 0x00020000);
   }
   const uint32_t vo0 = (uint32_t)((8 * h) * JD + row) * 4;
-  // the next tile's per-frame vectors, held as frame pairs so that the scaling below is
-  // one packed multiply per pair with no register shuffles
-  f2 nx[R + RV][4];
-  auto vec_load = [&](int ft) {
+  // per-frame vectors as frame pairs, in two register sets: a tile computes from one
+  // while the next tile's loads land in the other (the tile loop is unrolled by two), so
+  // no vector is copied or rescaled; only gs^0 takes its factor c^0 2^eg per tile
+  f2 nxa[R + RV][4], nxb[R + RV][4];
+  auto vec_load = [&](f2 (&nx)[R + RV][4], int ft) {
 #pragma unroll
     for (int v = 0; v < 8; ++v) {
       const uint32_t so = (uint32_t)((ft * 16 + v) * JD) * 4;
@@ -1729,38 +1769,32 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
   };
 
   f16v acc[CAP];
-  f2 gb[CAP];
+  float gb[CAP];
 #pragma unroll
   for (int k = 0; k < CAP; ++k) {
-    gb[k] = f2{0.f, 0.f};
+    gb[k] = 0.f;
     acc[k] = f16v{};
   }
   if (ft0 < ft1) {
     stage_load(ft0);
-    vec_load(ft0);
+    vec_load(nxa, ft0);
     stage_store(0);
     if (ft0 + 1 < ft1) stage_load(ft0 + 1);
   }
   const int xoff = CG * 4 + (n * 16 + ((h ^ ((n >> 3) & 1)) * 8)) * 2;
   const float s0 = c0 * sg;
-  for (int ft = ft0; ft < ft1; ++ft) {
-    const int buf = (ft - ft0) & 1;
-    // this tile's vectors, scaled by 2^eg (c^0 folded into gs^0): frame pairs (v, v + 1)
-    f2 fv[R + RV][4];
+  auto tile = [&](auto bufc, const f2 (&cur)[R + RV][4], f2 (&nxt)[R + RV][4], int ft) {
+    constexpr int buf = decltype(bufc)::value;
+    f2 g0[4];
 #pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      fv[0][v] = nx[0][v] * s0;
-#pragma unroll
-      for (int a = 1; a < R + RV; ++a) fv[a][v] = nx[a][v] * sg;
-    }
+    for (int v = 0; v < 4; ++v) g0[v] = cur[0][v] * s0;
     __syncthreads();   // tile ft staged in buf; buf ^ 1 (tile ft - 1) is free
     if (ft + 1 < ft1) {
       stage_store(buf ^ 1);
       if (ft + 2 < ft1) stage_load(ft + 2);
     }
-    // unconditional (the last tile reloads itself): a conditional load merges the old
-    // and new vectors and costs a register copy of every vector per tile
-    vec_load(ft + 1 < ft1 ? ft + 1 : ft);
+    // unconditional (the last tile reloads itself): no branch around the loads
+    vec_load(nxt, ft + 1 < ft1 ? ft + 1 : ft);
     const unsigned char* sb = stg[buf];
 #pragma unroll
     for (int k = 0; k < CAP; ++k) {
@@ -1768,7 +1802,7 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
       const float* ckf = reinterpret_cast<const float*>(ck);
       f2 gu[4];
 #pragma unroll
-      for (int v = 0; v < 4; ++v) gu[v] = fv[0][v];
+      for (int v = 0; v < 4; ++v) gu[v] = g0[v];
 #pragma unroll
       for (int r = 0; r < RV; ++r) {
         const float* cp = ckf + ((r * 2 + 0) * 4 + wv) * 16 + 8 * h;
@@ -1778,37 +1812,34 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
         const f2 g2[4] = {f2{ga[0], ga[1]}, f2{ga[2], ga[3]}, f2{gbv[0], gbv[1]}, f2{gbv[2], gbv[3]}};
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          gu[v] = __builtin_elementwise_fma(c2[v], fv[r + 1][v], gu[v]);
-          gu[v] = __builtin_elementwise_fma(g2[v], fv[R + r][v], gu[v]);
+          gu[v] = __builtin_elementwise_fma(c2[v], cur[r + 1][v], gu[v]);
+          gu[v] = __builtin_elementwise_fma(g2[v], cur[R + r][v], gu[v]);
         }
       }
-      gb[k] += (gu[0] + gu[1]) + (gu[2] + gu[3]);
+      const f2 gq = (gu[0] + gu[1]) + (gu[2] + gu[3]);
+      gb[k] += gq[0] + gq[1];
       h8 bh, bl;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        // hi: the low 13 mantissa bits cleared (exact in fp16); lo = f16(gu' - hi)
-        const f2 hi = __builtin_bit_cast(f2, __builtin_bit_cast(u2, gu[v]) & 0xFFFFE000u);
-        const f2 lo = gu[v] - hi;
-        const h2 ph = __builtin_convertvector(hi, h2);   // v_cvt_pk_f16_f32 (exact for hi)
-        const h2 pl = __builtin_convertvector(lo, h2);
-        bh[2 * v] = ph[0];
-        bh[2 * v + 1] = ph[1];
-        bl[2 * v] = pl[0];
-        bl[2 * v + 1] = pl[1];
-      }
+      split8h(gu, bh, bl);
       const h8 xh = *reinterpret_cast<const h8*>(ck + xoff);
       const h8 xl = *reinterpret_cast<const h8*>(ck + xoff + D * 16 * 2);
       acc[k] = mfma32h(xh, bh, acc[k]);
       acc[k] = mfma32h(xh, bl, acc[k]);
       acc[k] = mfma32h(xl, bh, acc[k]);
     }
+  };
+  using S0 = std::integral_constant<int, 0>;
+  using S1 = std::integral_constant<int, 1>;
+  for (int ft = ft0; ft < ft1; ft += 2) {
+    tile(S0{}, nxa, nxb, ft);
+    if (ft + 1 >= ft1) break;
+    tile(S1{}, nxb, nxa, ft + 1);
   }
   float* gw = gwp + (size_t)s * pstride;
   float* gbo = gbp + (size_t)s * pstride;
   const float un = srf_exp2i(-(bx + eg)), ug = srf_exp2i(-eg);
 #pragma unroll
   for (int k = 0; k < CAP; ++k) {
-    const float a = gb[k][0] + gb[k][1];
+    const float a = gb[k];
     float pa, pb;
     xpair32(a, pa, pb);
     if (k >= ncap || !wave_on) continue;
