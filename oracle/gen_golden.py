@@ -9,6 +9,8 @@ Run in the build container (needs /root/reference for the flag fixtures):
 * model_*.npz: SRF forward fixtures from the numpy float64 oracle
   (parity vs TF unpinned: TensorFlow is not installed), cross-checked at
   generation time against the float64 torch mirror; gradients from the mirror.
+* model_*_eval.npz: the same models in evaluation mode (EVAL_CASES); regenerate
+  some with ``python -m oracle.gen_golden c2_mini_eval c3_real_eval``.
 """
 import json
 import os
@@ -330,6 +332,117 @@ def gen_dp(only=()):
         print(name, out['nll'])
 
 
+# Evaluation-mode fixtures (training=False: BatchNorm on its moving statistics, no
+# dropout), model_<base>_eval.npz.  Parameters, feats, lengths and labels are the
+# base fixture's ('base' names it; nothing of it is stored again).  The moving
+# statistics are the oracle's batch mean / unbiased variance of an independently
+# seeded batch (regen_feats(seed + 1000 + offset, [max(8, l - 5) ...])), rounded to
+# float32: close to the data's own statistics, as in a trained model, not equal.
+#   logits / nll: the oracle with bn_training=False (nll: ctc_batch, ceil lengths);
+#   greedy_ceil_json / greedy_floor_json: best path at ceil(len/4) (validation) and
+#     len // 4 (process_test_step, trainer_sr.py:110);
+#   margin_ratio: min over the frames below the ceil length of
+#     (top1 - top2) / (1e-4 (1 + max(|top1|, |top2|))) -- at >= EVAL_MARGIN no
+#     implementation within the logit tolerance 1e-4 (1 + |ref|) can flip a label;
+#   m32_err: max |m32 - o64| / (1 + |o64|) of the float32 torch mirror in eval mode,
+#     required <= EVAL_M32 (half the GPU tolerance).
+# 'offset' is the smallest of 0..15 meeting both conditions; none: an error.
+EVAL_CASES = {n + '_eval': n for n in ('c1_mini', 'c2_mini', 'c3_mini_sdr', 'c2_mini_einsum', 'c2_mini_lowmemory',
+                                       'c3_mini_sdr_lowmemory', 'c4_mini', 'c4_real', 'c3_real', 'c5_real',
+                                       # the fp8-emulating float64 mirror in eval mode: 'logits' / 'nll'
+                                       # are the emulation's, 'logits_o64' / 'nll_o64' the plain oracle's
+                                       # on the same moving statistics; no m32 condition
+                                       'c5_real_fp8')}
+EVAL_MARGIN = 10.0
+EVAL_M32 = 0.5e-4
+EVAL_TOL = 1e-4
+
+
+def margin_ratio(logits, lens):
+    """Smallest top-1 / top-2 gap over the frames below ``lens``, in units of the
+    logit tolerance EVAL_TOL (1 + max(|top1|, |top2|))."""
+    r = np.inf
+    for b, l in enumerate(lens):
+        srt = np.sort(logits[b, :l], axis=-1)
+        t1, t2 = srt[:, -1], srt[:, -2]
+        r = min(r, float(((t1 - t2) / (EVAL_TOL * (1 + np.maximum(np.abs(t1), np.abs(t2))))).min()))
+    return r
+
+
+def eval_moving_stats(P, sh, seed, offset, lens):
+    """{bn{k}.moving_mean / moving_var} (float32) from the independent batch."""
+    lens2 = [max(8, l - 5) for l in lens]
+    feats2 = regen_feats(seed + 1000 + offset, lens2, sh.feat_dim)
+    _, stats = so.cnn_fe(P, sh, feats2, np.array(lens2, dtype=np.int32), bn_training=True)
+    out = {}
+    for k, (mu, var) in enumerate(stats):
+        out[f'bn{k}.moving_mean'] = mu.astype(np.float32)
+        out[f'bn{k}.moving_var'] = var.astype(np.float32)
+    return out
+
+
+def gen_eval(only=()):
+    sys.path.insert(0, ROOT)
+    from tests.helpers import load_model_fixture
+    for name, base in EVAL_CASES.items():
+        if only and name not in only:
+            continue
+        kw, sh, P, z = load_model_fixture(base)
+        fp8 = base in FP8_CASES
+        big = 'feats_seed' in z
+        feats, inp_len, labels, tar_len = z['feats'], z['inp_len'], z['labels'], z['tar_len']
+        lens = [int(l) for l in inp_len]
+        ceil_len, floor_len = np.ceil(inp_len / 4).astype(int), (inp_len // 4).astype(int)
+        T = int(inp_len.max())
+        tf, tl = torch.tensor(feats[:, :T]), torch.tensor(inp_len)
+        tried = []
+        for offset in range(16):
+            mv = eval_moving_stats(P, sh, int(z['seed']), offset, lens)
+            Pe = dict(P, **{k: v.astype(np.float64) for k, v in mv.items()})
+            o64 = so.srf_forward(Pe, sh, feats, inp_len, bn_training=False)
+            extra = {}
+            if fp8:
+                bf = _c5_bf16_layers(sh)
+                with torch.no_grad():
+                    logits = nm.NaiveMirror(sh, Pe, tile=False, fp8_pose=bf)(tf, tl, bn_training=False).numpy()
+                extra = {'logits_o64': o64.astype(np.float32),
+                         'nll_o64': so.ctc_batch(o64, labels, inp_len, tar_len, sh.class_n),
+                         'bf16_layers': np.array(bf, dtype=np.int32)}
+            else:
+                logits = o64
+            ratio = margin_ratio(logits, ceil_len)
+            if ratio < EVAL_MARGIN:
+                tried.append((offset, 'margin', ratio))
+                continue
+            if not fp8:
+                with torch.no_grad():
+                    m64 = nm.NaiveMirror(sh, Pe, tile=not big)(tf, tl, bn_training=False).numpy()
+                    m32 = nm.NaiveMirror(sh, Pe, dtype=torch.float32, tile=not big)(
+                        tf.float(), tl, bn_training=False).double().numpy()
+                assert np.abs(m64 - o64).max() < 1e-9, ('oracle/mirror disagree (eval)', np.abs(m64 - o64).max())
+                m32_err = float((np.abs(m32 - o64) / (1 + np.abs(o64))).max())
+                if m32_err > EVAL_M32:
+                    tried.append((offset, 'm32', m32_err))
+                    continue
+                extra['m32_err'] = np.array(m32_err)
+            break
+        else:
+            raise RuntimeError(f'{name}: no offset in 0..15 meets the conditions: {tried}')
+        blank = sh.class_n - 1
+        out = {'base': np.array(base), 'offset': np.array(offset),
+               'logits': logits if not big else logits.astype(np.float32),
+               'nll': so.ctc_batch(logits, labels, inp_len, tar_len, sh.class_n),
+               'greedy_ceil_json': np.array(json.dumps(so.greedy_decode(logits, ceil_len, blank))),
+               'greedy_floor_json': np.array(json.dumps(so.greedy_decode(logits, floor_len, blank))),
+               'margin_ratio': np.array(ratio)}
+        out.update(mv)
+        out.update(extra)
+        np.savez_compressed(os.path.join(GOLD, f'model_{name}.npz'), **out)
+        print(name, 'offset', offset, 'rejected', tried, 'margin_ratio', ratio, 'm32_err',
+              float(extra.get('m32_err', np.nan)), 'nll', out['nll'],
+              'eval vs training-mode logits', float(np.abs(logits - z['logits']).max()))
+
+
 def gen_flags():
     sys.path.insert(0, REF)
     from tfsr.helper.common_helper import Logger, ParseOption  # reference parser, read-only
@@ -404,3 +517,5 @@ if __name__ == '__main__':
         gen_refinit([n for n in only if n in REFINIT_CASES])
     if not only or any(n in FP8_CASES for n in only):
         gen_fp8([n for n in only if n in FP8_CASES])
+    if not only or any(n in EVAL_CASES for n in only):   # last: they read their base fixtures
+        gen_eval([n for n in only if n in EVAL_CASES])

@@ -354,7 +354,10 @@ class NaiveMirror(torch.nn.Module):
     def P(self, name):
         return self.p[name.replace('.', '__')]
 
-    def forward(self, feats, inp_len, drop=None):
+    def forward(self, feats, inp_len, drop=None, bn_training=True):
+        """bn_training=False: BatchNormalization in inference mode, normalising with the
+        ``bn{k}.moving_mean`` / ``bn{k}.moving_var`` the mirror was built with
+        (``srf_oracle.batch_norm(training=False)``)."""
         sh = self.shape
         x = feats.unsqueeze(-1)
         for k in range(sh.cnn_n):
@@ -365,7 +368,11 @@ class NaiveMirror(torch.nn.Module):
                 x2 = x2 * drop[f'conv{k}b']
             x = torch.maximum(x1, x2)
             x = feat_mask(x, inp_len, 2 ** (k + 1))
-            x, _, _ = batch_norm_train(x, self.P(f'bn{k}.gamma'), self.P(f'bn{k}.beta'))
+            if bn_training:
+                x, _, _ = batch_norm_train(x, self.P(f'bn{k}.gamma'), self.P(f'bn{k}.beta'))
+            else:
+                mu, var = self.buffers_[f'bn{k}.moving_mean'], self.buffers_[f'bn{k}.moving_var']
+                x = (x - mu) * torch.rsqrt(var + so.BN_EPS) * self.P(f'bn{k}.gamma') + self.P(f'bn{k}.beta')
             x = feat_mask(x, inp_len, 2 ** (k + 1))
         B, T2, F2, C = x.shape
         emb = x.reshape(B, T2, F2 * C) @ self.P('proj.kernel') + self.P('proj.bias')

@@ -51,6 +51,25 @@ def load_model_fixture(name):
     return kw, sh, P, arrays
 
 
+def load_eval_fixture(name):
+    """The evaluation-mode fixture of base fixture ``name`` (model_<name>_eval.npz,
+    oracle/gen_golden.py EVAL_CASES): load_model_fixture(base)'s tuple with the stored
+    BatchNorm moving statistics merged into the parameters (SequenceRouter.load_params
+    and the oracle both read them there), plus the eval arrays -- 'logits', 'nll',
+    'greedy_ceil' / 'greedy_floor' (lists), 'margin_ratio', 'm32_err', 'offset'."""
+    e = np.load(os.path.join(GOLD, f'model_{name}_eval.npz'), allow_pickle=False)
+    kw, sh, P, z = load_model_fixture(str(e['base']))
+    ev = {k: e[k] for k in e.files}
+    P = dict(P)
+    for k in e.files:
+        if k.endswith('.moving_mean') or k.endswith('.moving_var'):
+            assert ev[k].dtype == np.float32 and k in P, k
+            P[k] = ev[k].astype(np.float64)
+    ev['greedy_ceil'] = json.loads(str(e['greedy_ceil_json']))
+    ev['greedy_floor'] = json.loads(str(e['greedy_floor_json']))
+    return kw, sh, P, z, ev
+
+
 def gradient_mismatches(z, grad_of, rel=2e-3, abs_=1e-5):
     """Compare a model's parameter gradients with a fixture's: full arrays
     ('grad.<name>') or seeded samples ('gidx.'/'gval.' + 'gstat.' = max|g|, L2 norm).

@@ -8,7 +8,7 @@ import torch
 
 from oracle import naive_mirror as nm
 from oracle import srf_oracle as so
-from tests.helpers import load_model_fixture
+from tests.helpers import load_eval_fixture, load_model_fixture
 
 
 @pytest.mark.parametrize('name', ['c1_mini', 'c2_mini', 'c3_mini_sdr', 'c2_mini_einsum', 'c2_mini_lowmemory',
@@ -20,6 +20,56 @@ def test_oracle_reproduces_fixture(name):
     nll = so.ctc_batch(logits, z['labels'], z['inp_len'], z['tar_len'], sh.class_n)
     assert np.abs(nll - z['nll']).max() < 1e-8
     assert so.greedy_decode(logits, np.ceil(z['inp_len'] / 4).astype(int), sh.class_n - 1) == z['greedy']
+
+
+EVAL_MINIS = ['c1_mini', 'c2_mini', 'c3_mini_sdr', 'c2_mini_einsum', 'c2_mini_lowmemory', 'c3_mini_sdr_lowmemory',
+              'c4_mini']
+
+
+@pytest.mark.parametrize('name', EVAL_MINIS)
+def test_oracle_reproduces_eval_fixture(name):
+    """Evaluation mode (BatchNorm on the fixture's moving statistics): the oracle
+    recomputes the stored logits, NLL and both greedy decodes (ceil lengths as the
+    validation step uses, floor lengths as the test step does)."""
+    kw, sh, P, z, ev = load_eval_fixture(name)
+    logits = so.srf_forward(P, sh, z['feats'], z['inp_len'], bn_training=False)
+    assert np.abs(logits - ev['logits']).max() < 1e-9
+    assert np.abs(logits - z['logits']).max() > 1e-2     # not the training-mode logits
+    nll = so.ctc_batch(logits, z['labels'], z['inp_len'], z['tar_len'], sh.class_n)
+    assert np.abs(nll - ev['nll']).max() < 1e-8
+    blank = sh.class_n - 1
+    assert so.greedy_decode(logits, np.ceil(z['inp_len'] / 4).astype(int), blank) == ev['greedy_ceil']
+    assert so.greedy_decode(logits, z['inp_len'] // 4, blank) == ev['greedy_floor']
+
+
+@pytest.mark.parametrize('name', ['c2_mini', 'c3_mini_sdr'])
+def test_mirror_eval_mode_matches_oracle(name):
+    """NaiveMirror(bn_training=False) in float64 equals the oracle in eval mode."""
+    kw, sh, P, z, ev = load_eval_fixture(name)
+    with torch.no_grad():
+        got = nm.NaiveMirror(sh, P)(torch.tensor(z['feats']), torch.tensor(z['inp_len']), bn_training=False).numpy()
+    assert np.abs(got - so.srf_forward(P, sh, z['feats'], z['inp_len'], bn_training=False)).max() < 1e-10
+
+
+def test_eval_fixtures_meet_their_conditions():
+    """Every model_*_eval.npz: the greedy margin is >= 10 logit tolerances (so a GPU
+    within tolerance cannot flip a label and bit-exact decoding is a fair demand),
+    and the float32 mirror's distance from the oracle is within half the GPU
+    tolerance wherever that condition applies (not the fp8 emulation)."""
+    import glob
+    import os
+    from oracle import gen_golden as gg
+    from tests.helpers import GOLD
+    files = sorted(glob.glob(os.path.join(GOLD, 'model_*_eval.npz')))
+    assert {os.path.basename(f)[6:-4] for f in files} == set(gg.EVAL_CASES)
+    for f in files:
+        e = np.load(f, allow_pickle=False)
+        assert float(e['margin_ratio']) >= gg.EVAL_MARGIN, f
+        assert 0 <= int(e['offset']) <= 15, f
+        if str(e['base']) in gg.FP8_CASES:
+            assert 'm32_err' not in e.files and 'logits_o64' in e.files, f
+        else:
+            assert 0 < float(e['m32_err']) <= gg.EVAL_M32, f
 
 
 @pytest.mark.parametrize('caps_type', ['naive', 'einsum', 'lowmemory'])

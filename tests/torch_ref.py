@@ -69,10 +69,15 @@ def time_mask(inp_len, div, T, dtype):
     return (torch.arange(T, device=inp_len.device)[None, :] < lens[:, None]).to(dtype)
 
 
-def cnnfe(feats, inp_len, P, drop=None):
+def cnnfe(feats, inp_len, P, drop=None, return_stats=False, moving=None):
     """CapsulationLayer with BN in training mode; P: dict of tensors keyed
-    conv0a_kernel ...; drop: dict of multiplier tensors or None."""
+    conv0a_kernel ...; drop: dict of multiplier tensors or None.
+    return_stats: also return [(batch mean, UNBIASED batch variance)] per stage, over
+    all positions (the masked padded ones included) -- what Keras' fused BN feeds the
+    moving averages.  moving: (mean0, var0, mean1, var1) switches BN to inference
+    mode on those statistics (sequence_router.py:78 with training=False)."""
     x = feats.unsqueeze(-1)
+    stats = []
     for k in range(2):
         x1 = conv2d_same(x, P[f'conv{k}a_kernel'], P[f'conv{k}a_bias'], 2)
         x2 = conv2d_same(x, P[f'conv{k}b_kernel'], P[f'conv{k}b_bias'], 2)
@@ -82,11 +87,16 @@ def cnnfe(feats, inp_len, P, drop=None):
         x = torch.maximum(x1, x2)
         m = time_mask(inp_len, 2 ** (k + 1), x.shape[1], x.dtype)[:, :, None, None]
         x = x * m
-        mu = x.mean(dim=(0, 1, 2))
-        var = x.var(dim=(0, 1, 2), unbiased=False)
+        if moving is None:
+            mu = x.mean(dim=(0, 1, 2))
+            var = x.var(dim=(0, 1, 2), unbiased=False)
+            n = x.numel() // x.shape[-1]
+            stats.append((mu.detach(), var.detach() * n / max(n - 1, 1)))
+        else:
+            mu, var = moving[2 * k], moving[2 * k + 1]
         x = (x - mu) * torch.rsqrt(var + 1e-3) * P[f'bn{k}_gamma'] + P[f'bn{k}_beta']
         x = x * m
-    return x
+    return (x, stats) if return_stats else x
 
 
 def squash(s, dim=-1):
