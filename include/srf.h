@@ -413,6 +413,31 @@ int srf_ctc_loss(const float* logits, const int* labels, const int* label_len, c
                  int C, int Lmax, int blank, float grad_scale, float* nll, float* grad, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- Chunked streaming inference (srf_amd/streaming.py) --------------------
+ * srf_ctc_greedy_n: best-path decoding (per-frame arg-max, repeats merged, blanks
+ * dropped; trainer_sr.py's greedy hypothesis) of one chunk of logits [B][n][C], of which
+ * the first n_valid[b] frames of stream b count (clamped to [0, n]).  prev [B] is read
+ * and written: the arg-max of the stream's last decoded frame, -1 before its first, so a
+ * label that repeats across a chunk edge is merged.  labels [B][n] receives each
+ * stream's new labels compacted to the front, count [B] how many.  On equal logits the
+ * lowest class index wins (torch.argmax).  One wave per stream; any C >= 2, n >= 0. */
+int srf_ctc_greedy_n(const float* logits, const int* n_valid, int B, int n, int C, int blank, int* prev, int* labels,
+                     int* count, void* stream);
+/* srf_stream_advance_n: up to SRF_STREAM_ADVANCE_MAX sliding state buffers, each
+ * [B][rows_per_stream][row_bytes], move rows [shift, shift + keep) of every stream to
+ * rows [0, keep) in one launch (the other rows keep or lose their content: undefined).
+ * Source and destination may overlap (keep > shift): one workgroup per (buffer, stream)
+ * walks the block in ascending tiles, each read whole into registers before a barrier
+ * and stored after it.  shift + keep <= rows_per_stream; shift = 0 or keep = 0 moves
+ * nothing. */
+#define SRF_STREAM_ADVANCE_MAX 32
+typedef struct {
+  void* ptr;
+  size_t row_bytes;
+  int rows_per_stream, shift, keep;
+} srf_stream_buf;
+int srf_stream_advance_n(const srf_stream_buf* bufs, int n_bufs, int B, void* stream);
+
 /* ---- Fused Adam over one flat parameter buffer ----------------------------
  * Replaces the Keras Adam apply of trainer_sr.py:71 / train_helper.py:60-70:
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= alpha m / (sqrt(v) + eps),

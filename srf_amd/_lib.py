@@ -37,6 +37,14 @@ class CapsnormRange(ctypes.Structure):
 
 _cn_ranges = ctypes.POINTER(CapsnormRange)
 
+STREAM_ADVANCE_MAX = 32   # SRF_STREAM_ADVANCE_MAX
+
+
+class StreamBuf(ctypes.Structure):
+    """srf_stream_buf: one sliding state buffer for srf_stream_advance_n."""
+    _fields_ = [('ptr', _vp), ('row_bytes', _c_size), ('rows_per_stream', _c_int), ('shift', _c_int),
+                ('keep', _c_int)]
+
 # name -> (restype, argtypes); mirrors include/srf.h one to one.
 _SIGNATURES = {
     'srf_version': (_c_int, []),
@@ -128,6 +136,8 @@ _SIGNATURES = {
                           + [_vp] * 9 + [_c_size, _vp]),
     'srf_ctc_workspace': (_c_size, [_c_int] * 4),
     'srf_ctc_loss': (_c_int, [_vp] * 4 + [_c_int] * 5 + [ctypes.c_float, _vp, _vp, _vp, _c_size, _vp]),
+    'srf_ctc_greedy_n': (_c_int, [_vp, _vp] + [_c_int] * 4 + [_vp, _vp, _vp, _vp]),
+    'srf_stream_advance_n': (_c_int, [ctypes.POINTER(StreamBuf), _c_int, _c_int, _vp]),
     'srf_adam_step': (_c_int, [_vp, _vp, _vp, _vp, _c_size, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _vp]),
 }

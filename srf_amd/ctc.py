@@ -41,6 +41,18 @@ def greedy_decode(logits, lengths, blank_index):
     return out
 
 
+def greedy_decode_device(logits, n_valid, blank_index, prev):
+    """Incremental best-path decoding on the device (srf_ctc_greedy_n): the labels that
+    the first n_valid[b] frames of this chunk of logits [B, n, C] add to stream b's
+    hypothesis.  prev [B] int32 carries the last frame's arg-max from chunk to chunk
+    (-1 at a stream's start) and is updated in place, so a label repeated across a chunk
+    edge is merged as greedy_decode merges it.  Returns device tensors (labels [B, n]
+    int32, each stream's compacted to the front, and count [B] int32): the logits are
+    not copied to the host."""
+    n_valid = n_valid.to(device=logits.device, dtype=torch.int32).contiguous()
+    return ops.ctc_greedy_chunk(logits.contiguous(), n_valid, blank_index, prev)
+
+
 def beam_search_decode(logits, lengths, blank_index, beam_width=100):
     """tf.nn.ctc_beam_search_decoder(time-major logits, lengths, beam_width,
     top_paths=1) as process_test_step calls it (trainer_sr.py:109-112), on the host

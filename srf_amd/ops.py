@@ -553,6 +553,47 @@ def ctc_loss(logits, labels, label_len, logit_len, blank):
     return CtcLoss.apply(logits, _i32(labels), _i32(label_len), _i32(logit_len), blank)
 
 
+def ctc_greedy_chunk(logits, n_valid, blank, prev):
+    """srf_ctc_greedy_n: best-path labels of one chunk of logits [B, n, C] (the first
+    n_valid[b] frames of stream b), continuing from prev [B] int32 (the last frame's
+    arg-max, -1 at a stream's start; updated in place).  Returns (labels [B, n] int32,
+    compacted per stream, count [B] int32), both on the device."""
+    B, n, C = logits.shape
+    _check_dev('logits', logits, (B, n, C))
+    for name, t in (('n_valid', n_valid), ('prev', prev)):
+        if not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous int32 device tensor of shape ({B},)')
+    labels = torch.empty((B, n), device=logits.device, dtype=torch.int32)
+    count = torch.empty(B, device=logits.device, dtype=torch.int32)
+    _lib.check(_lib.lib().srf_ctc_greedy_n(_ptr(logits), _ptr(n_valid), B, n, C, int(blank), _ptr(prev), _ptr(labels),
+                                           _ptr(count), _stream()), 'srf_ctc_greedy_n')
+    return labels, count
+
+
+def stream_advance(bufs):
+    """srf_stream_advance_n: bufs = [(tensor [B, rows, ...], rows, shift, keep)]; rows
+    [shift, shift + keep) of every stream of every tensor move to rows [0, keep), in
+    place, in one launch per _lib.STREAM_ADVANCE_MAX buffers."""
+    if not bufs:
+        return
+    B = bufs[0][0].shape[0]
+    items = []
+    for t, rows, shift, keep in bufs:
+        if not t.is_cuda or not t.is_contiguous() or t.dim() < 2 or t.shape[0] != B or t.shape[1] != rows:
+            raise ValueError(f'stream_advance: a contiguous device tensor [{B}, {rows}, ...] expected, got '
+                             f'{tuple(t.shape)}')
+        if shift < 0 or keep < 0 or shift + keep > rows:
+            raise ValueError(f'stream_advance: rows [{shift}, {shift} + {keep}) outside [0, {rows})')
+        row_bytes = t.numel() // (B * rows) * t.element_size()
+        if row_bytes:
+            items.append(_lib.StreamBuf(ptr=t.data_ptr(), row_bytes=row_bytes, rows_per_stream=rows, shift=shift,
+                                        keep=keep))
+    for c in range(0, len(items), _lib.STREAM_ADVANCE_MAX):
+        part = items[c:c + _lib.STREAM_ADVANCE_MAX]
+        _lib.check(_lib.lib().srf_stream_advance_n((_lib.StreamBuf * len(part))(*part), len(part), B, _stream()),
+                   'srf_stream_advance_n')
+
+
 # ---------------------------------------------------------------------------
 # Fault word of the grouped SDR recurrences (srf_set_fault_flag): one per process
 GROUP_RESERVE_CUS = 4   # CUs a grouped launch leaves free (srf_group.h kReserveCUs)

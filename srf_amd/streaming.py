@@ -1,0 +1,337 @@
+"""Chunked streaming inference with carried routing state.
+
+``StreamingRouter(model, n_streams)`` feeds ``n_streams`` utterances to an evaluation-mode
+``SequenceRouter`` chunk by chunk, in lock step, and emits every output frame as soon as
+the input it depends on has arrived.  After ``finish()`` the concatenated logits are
+those of ``model(all pushed feats, input_lengths=lens, training=False)``.
+
+What an output frame needs of the future:
+
+* CNN front end: output frame o reads input frames 4o .. 4o + 6 (two stride-2 3x3
+  convolutions, TF "same" padding at a length that is a multiple of 4);
+* primary capsules: frame o reads CNN-FE frames o - 1 .. o + 1 (the encaps 3x3);
+* routing layer l: frame t reads its input frames t - lpad .. t + rpad (the window), and
+  with sequential dynamic routing (SDR) its own output frame t - 1.
+
+So after P pushed input frames P/4 - 1 CNN-FE frames are final, P/4 - 2 primary-capsule
+frames and P/4 - 2 - l * rpad frames of routing layer l (``frames_final``): the model's
+lookahead is 2 + L * rpad output frames.
+
+State: the last 4 input frames; the CNN-FE frames the primary capsules still need; and per
+routing layer a sliding buffer of its input frames (SDR: also of its output frames, for
+the carry).  The routing buffers share one timeline -- local frame = global frame - base
+-- so a layer's LayerNorm writes straight into the next layer's buffer, and one launch
+(srf_stream_advance_n) slides them all.  Everything runs on the current stream under
+``torch.no_grad()``: no side streams, no graph capture.
+"""
+import torch
+
+from . import _lib, ctc, ops
+
+_NO_END = 1 << 30   # length of a stream whose end is not known yet (device side)
+
+
+def frames_final(pushed, n_layers, rpad, finished=False):
+    """Output frames that are final per stage after ``pushed`` input frames (a multiple
+    of 4): [CNN-FE, primary capsules, routing layer 1, ..., routing layer n_layers].  The
+    last entry is what has been emitted.  ``finished``: the utterance ends at ``pushed``,
+    every stage is complete."""
+    if pushed % 4 or pushed < 0:
+        raise ValueError(f'pushed frames must be a non-negative multiple of 4, got {pushed}')
+    if finished:
+        return [pushed // 4] * (n_layers + 2)
+    out = [max(0, pushed // 4 - 1)]
+    out.append(max(0, out[0] - 1))
+    for _ in range(n_layers):
+        out.append(max(0, out[-1] - rpad))
+    return out
+
+
+def stream_schedule(pushes, n_layers, rpad):
+    """``frames_final`` after each push of ``pushes`` (input frames per chunk), then after
+    ``finish()``: len(pushes) + 1 rows."""
+    rows, total = [], 0
+    for n in pushes:
+        total += n
+        rows.append(frames_final(total, n_layers, rpad))
+    rows.append(frames_final(total, n_layers, rpad, finished=True))
+    return rows
+
+
+def check_ended(lengths, ended, pushed, n):
+    """Validate one push's ``ended`` against the streams' declared lengths (None: not
+    declared) and return the new list.  ``pushed`` frames came before this chunk of
+    ``n``; a declared length must lie in [pushed, pushed + n] and is declared once."""
+    if ended is None:
+        return list(lengths)
+    vals = [int(e) for e in (ended.tolist() if hasattr(ended, 'tolist') else ended)]
+    if len(vals) != len(lengths):
+        raise ValueError(f'ended has {len(vals)} entries for {len(lengths)} streams')
+    new = list(lengths)
+    for b, e in enumerate(vals):
+        if e == -1:
+            continue
+        if e < -1:
+            raise ValueError(f'stream {b}: ended must be a length or -1, got {e}')
+        if lengths[b] is not None:
+            raise ValueError(f'stream {b}: its length was already declared ({lengths[b]})')
+        if e < pushed:
+            raise ValueError(f'stream {b}: length {e} lies before this chunk (frames {pushed} .. {pushed + n}): '
+                             'its frames were already emitted unmasked; declare the end with the chunk it lies in')
+        if e > pushed + n:
+            raise ValueError(f'stream {b}: length {e} lies beyond this chunk (frames {pushed} .. {pushed + n})')
+        new[b] = e
+    return new
+
+
+class StreamOut:
+    """What one ``push`` / ``finish`` emitted: output frames [t0, t0 + m) of every
+    stream.  ``logits`` [B, m, C] (device); ``labels``: per stream, the greedy labels
+    these frames added (fetched from the device on first use)."""
+
+    def __init__(self, router, t0, logits):
+        self._router, self.t0, self.logits, self._labels = router, t0, logits, None
+
+    @property
+    def labels(self):
+        if self._labels is None:
+            self._router._fetch_labels()
+        return self._labels
+
+
+class StreamingRouter:
+    """``n_streams`` utterances through ``model`` (evaluation mode; naive or lowmemory,
+    DR or SDR) in lock step, in chunks of at most ``max_chunk`` input frames.
+
+    ``push(feats, ended=None)`` / ``finish()`` return a ``StreamOut``; ``reset()`` starts
+    over; ``lookahead`` is 2 + L * rpad output frames; ``hypotheses`` the greedy labels so
+    far.  The model's parameters and BatchNorm moving statistics are read, never written."""
+
+    def __init__(self, model, n_streams, max_chunk=64):
+        if model.caps_type == 'einsum':
+            raise ValueError('the einsum variant cannot stream: its positional encoding needs the absolute frame '
+                             'index, which srf_primary_caps_fwd_ex does not take')
+        if model.pose_fp8:
+            raise ValueError('model_pose_fp8 is not supported by the streaming path')
+        if int(n_streams) < 1:
+            raise ValueError(f'n_streams must be >= 1, got {n_streams}')
+        if int(max_chunk) < 4 or int(max_chunk) % 4:
+            raise ValueError(f'max_chunk must be a positive multiple of 4 input frames, got {max_chunk}')
+        self.model, self.B, self.max_chunk = model, int(n_streams), int(max_chunk)
+        self.L, self.lpad, self.rpad = model.enc_num, model.lpad, model.rpad
+        self.lookahead = 2 + self.L * self.rpad
+        self.blank = model.class_n - 1
+        self.device = model.flat_params.device
+        # the routing buffers' timeline: the last layer's next frame D sits at local
+        # lpad + 1 (its window's left edge at 1, its SDR carry at lpad); the newest
+        # primary-capsule frame is at most max_chunk / 4 + L * rpad frames ahead of D
+        # (2 + L * rpad at finish), and an SDR pose at finish reads rpad zero frames more
+        self.cap = self.max_chunk // 4 + (self.L + 1) * self.rpad + self.lpad + 3
+        self._alloc()
+        self.reset()
+
+    # ------------------------------------------------------------------ state
+    def _alloc(self):
+        m, B, dev = self.model, self.B, self.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        self._emb, self._v, self._u, self._ws = [], [], [], []
+        nmax = max(self.max_chunk // 4, self.lookahead)   # frames one call makes final per layer
+        for l, (in_n, J, D, din) in enumerate(m.layer_shapes):
+            self._emb.append(torch.zeros((B, self.cap, in_n // m.window, din), **f32))
+            if m.is_context:
+                self._v.append(torch.zeros((B, self.cap, J, D), **f32))
+                self._u.append(torch.empty(B * nmax * in_n * J * D, **f32))
+                self._ws.append(self._recur_workspace(in_n, J, D))
+        self._tail = torch.zeros((B, 4, m.feat_dim_in), **f32)
+        self._len_dev = torch.full((B,), _NO_END, device=dev, dtype=torch.int32)
+        self._prev = torch.full((B,), -1, device=dev, dtype=torch.int32)
+
+    def _recur_workspace(self, in_n, J, D):
+        n = _lib.lib().srf_route_sdr_recur_workspace(self.B, in_n, J, D, self.model.route_iters)
+        return torch.zeros(max(n, 16), device=self.device, dtype=torch.uint8)
+
+    def reset(self):
+        """Every stream back at its start."""
+        for t in self._emb + self._v:
+            t.zero_()   # zero frames before the start: the window's padding and the SDR carry v_0 = 0
+        self._tail.zero_()
+        self._len_dev.fill_(_NO_END)
+        self._prev.fill_(-1)
+        self._x = None          # CNN-FE frames [_xg, ...) the primary capsules still need
+        self._xg = 0
+        self._base = -(self.lpad + 1)
+        self._pushed = 0
+        self._lengths = [None] * self.B
+        self._finished = False
+        self._hyp = [[] for _ in range(self.B)]
+        self._pending = []      # (StreamOut, labels, count) not yet fetched from the device
+
+    @property
+    def hypotheses(self):
+        """Per stream, the greedy labels of the frames emitted so far (frames below
+        ceil(len / 4))."""
+        self._fetch_labels()
+        return [list(h) for h in self._hyp]
+
+    def _fetch_labels(self):
+        for out, labels, count in self._pending:
+            labels, count = labels.cpu().tolist(), count.cpu().tolist()
+            out._labels = [labels[b][:count[b]] for b in range(self.B)]
+            for b in range(self.B):
+                self._hyp[b].extend(out._labels[b])
+        self._pending = []
+
+    # ------------------------------------------------------------------ stages
+    def _local_len(self, offset, frames):
+        """Input-frame lengths relative to a buffer that starts at input frame ``offset``
+        and spans ``frames`` of them; the buffer's length while the end is unknown."""
+        return (self._len_dev - offset).clamp_(0, frames)
+
+    def _cnnfe(self, buf, lens):
+        m = self.model
+        moving = [getattr(m, n) for n in ('bn0_moving_mean', 'bn0_moving_var', 'bn1_moving_mean', 'bn1_moving_var')]
+        return ops.cnnfe(buf, lens, [m.P(k) for k in ops.CNNFE_PARAMS], moving, False, 0.0, 0)
+
+    def _caps(self, x, lens):
+        m = self.model
+        return ops.primary_caps(x, lens, m.caps_inp_n, m.caps_inp_d, False, 0.0, 0.0, 0,
+                                [m.P(k) for k in ops.CAPS_PARAMS], m.proj_scale, False)
+
+    def _dr(self, l, x):
+        """DR layer l on the buffer slice x [B, Tx, N, din] -> v [B, Tx, J, D]."""
+        m = self.model
+        W, bias = m._identity.get(l, (m.P(f'W{l}'), m.P(f'b{l}')))
+        return ops.dynamic_routing(x, W, bias, m._geom(l, self.B, x.shape[1]))
+
+    def _norm(self, l, v):
+        m = self.model
+        return ops.CapsNorm.apply(v, m.P(f'ln_mid{l + 1}_gamma'), m.P(f'ln_mid{l + 1}_beta'), False, 0.0, 0, l)
+
+    def _head(self, v):
+        m, l = self.model, self.L - 1
+        return ops.CapsHead.apply(v, m.P(f'ln_mid{l + 1}_gamma'), m.P(f'ln_mid{l + 1}_beta'),
+                                  m.P('ln_output_gamma'), m.P('ln_output_beta'), False, 0.0, 0, l, m.length_eps)
+
+    def _sdr(self, l, t0, t1):
+        """SDR layer l over local frames [t0, t1): pose, the recurrence seeded from
+        v[t0 - 1], and (inner layers) LayerNorm into the next layer's buffer.  The
+        arguments are those of ops.SdrStack.forward's item()."""
+        m, B, T = self.model, self.B, self.cap
+        in_n, J, D, din = m.layer_shapes[l]
+        L_ = _lib.lib()
+        r = ops._sdr_r(t0=t0, t1=t1, emb=ops._ptr(self._emb[l]), W=ops._ptr(m.P(f'W{l}')), bias=ops._ptr(m.P(f'b{l}')),
+                       u=ops._ptr(self._u[l]), v0=t0, vn=t1 - t0, v=ops._ptr(self._v[l]), couplings=None,
+                       workspace=ops._ptr(self._ws[l]), workspace_bytes=self._ws[l].numel(), u_bf16=0, group=1)
+        st = ops._stream()
+        ops._sdr_call(L_.srf_route_sdr_pose_n, [r], B, T, in_n // m.window, din, m.lpad, m.rpad, J, D, 0, st,
+                      what='sdr_pose_n')
+        ops._sdr_call(L_.srf_route_sdr_recur_fwd_n, [r], B, T, in_n, J, D, m.route_iters, int(l == self.L - 1), st,
+                      what='sdr_recur_fwd_n')
+        if l < self.L - 1:
+            cn = _lib.CapsnormRange(t0=t0, t1=t1, layer=l, x=ops._ptr(self._v[l]),
+                                    gamma=ops._ptr(m.P(f'ln_mid{l + 1}_gamma')),
+                                    beta=ops._ptr(m.P(f'ln_mid{l + 1}_beta')), y=ops._ptr(self._emb[l + 1]),
+                                    stat=ops._ptr(self._stat(B * T)))
+            ops._cn_call(L_.srf_capsnorm_fwd_range_n, [cn], B, T, J * D, 0, 0.0, 0, st, what='capsnorm_fwd_range_n')
+
+    def _stat(self, rows):
+        s = getattr(self, '_stat_buf', None)
+        if s is None or s.shape[0] < rows:
+            s = self._stat_buf = torch.empty((rows, 4), device=self.device, dtype=torch.float32)
+        return s
+
+    def _advance(self, shift, keep):
+        ops.stream_advance([(t, self.cap, shift, keep) for t in self._emb + self._v])
+
+    def _greedy(self, logits, n_valid):
+        return ctc.greedy_decode_device(logits, n_valid, self.blank, self._prev)
+
+    # ------------------------------------------------------------------ the chunk step
+    def push(self, feats, ended=None):
+        """feats [B, n, feat_dim], n a multiple of 4 and at most max_chunk.  ``ended``
+        [B]: the total input length of a stream whose end lies in this chunk, else -1."""
+        if self._finished:
+            raise ValueError('push after finish(): call reset() to start new utterances')
+        if feats.dim() != 3 or feats.shape[0] != self.B or feats.shape[2] != self.model.feat_dim_in:
+            raise ValueError(f'feats must be [{self.B}, n, {self.model.feat_dim_in}], got {tuple(feats.shape)}')
+        n = feats.shape[1]
+        if n % 4 or n > self.max_chunk:
+            raise ValueError(f'a chunk holds a multiple of 4 input frames, at most max_chunk = {self.max_chunk}; '
+                             f'got {n}')
+        lengths = check_ended(self._lengths, ended, self._pushed, n)
+        if lengths != self._lengths:
+            self._lengths = lengths
+            self._len_dev.copy_(torch.tensor([_NO_END if e is None else e for e in lengths], dtype=torch.int32))
+        with torch.no_grad():
+            return self._step(feats.to(device=self.device, dtype=torch.float32), False)
+
+    def finish(self):
+        """End of every stream: the frames still held back by the lookahead.  A stream
+        that never declared a length ends with the last pushed frame."""
+        if self._finished:
+            raise ValueError('finish() was already called: call reset() to start new utterances')
+        with torch.no_grad():
+            out = self._step(None, True)
+        self._finished = True
+        return out
+
+    def _step(self, feats, finishing):
+        B, lpad, rpad = self.B, self.lpad, self.rpad
+        before = frames_final(self._pushed, self.L, rpad)
+        n = 0 if finishing else feats.shape[1]
+        P0, P1 = self._pushed, self._pushed + n
+        after = frames_final(P1, self.L, rpad, finished=finishing)
+        # CNN-FE on [4 kept | n new] (at finish: the kept frames alone, whose right edge is
+        # the utterance's): the buffer starts at input frame P0 - 4, a multiple of 4, so
+        # local output frame o is global frame P0 / 4 - 1 + o
+        if after[0] > before[0]:
+            buf = self._tail if finishing else torch.cat([self._tail, feats], dim=1)
+            y = self._cnnfe(buf.contiguous(), self._local_len(P0 - 4, buf.shape[1]))
+            lo = before[0] - (P0 // 4 - 1)
+            new = y[:, lo:lo + after[0] - before[0]]
+            self._x = new if self._x is None else torch.cat([self._x, new], dim=1)
+        if n:
+            self._tail = feats[:, -4:].clone()
+        self._pushed = P1
+        # primary capsules on the CNN-FE frames held: frame o needs frames o - 1 .. o + 1
+        # (the kernel's zero padding of e is the reference's at the utterance's two ends)
+        base = self._base
+        if after[1] > before[1]:
+            x = self._x.contiguous()
+            z = self._caps(x, self._local_len(4 * self._xg, 4 * x.shape[1]))
+            self._emb[0][:, before[1] - base:after[1] - base] = z[:, before[1] - self._xg:after[1] - self._xg]
+            xg = max(0, after[1] - 1)
+            self._x, self._xg = self._x[:, xg - self._xg:], xg
+        # routing layers, bottom up: layer l's frames [a, b) are final once its input is
+        # final up to b - 1 + rpad (at finish: up to the end, zero beyond it)
+        logits = None
+        for l in range(self.L):
+            a, b, hi = before[l + 2], after[l + 2], after[l + 1]
+            if b == a:
+                continue
+            t0, t1 = a - base, b - base
+            if self.model.is_context:
+                if finishing and rpad:
+                    self._emb[l][:, hi - base:hi - base + rpad].zero_()
+                self._sdr(l, t0, t1)
+                v = self._v[l][:, t0:t1]
+            else:
+                # the window's halo (lpad + rpad frames) is routed again with every chunk
+                v = self._dr(l, self._emb[l][:, t0 - lpad:min(t1 + rpad, hi - base)].contiguous())[:, lpad:lpad + b - a]
+                if l < self.L - 1:
+                    self._emb[l + 1][:, t0:t1] = self._norm(l, v.contiguous())
+            if l == self.L - 1:
+                logits = self._head(v.contiguous())
+        t0, m = before[-1], after[-1] - before[-1]
+        if logits is None:
+            logits = torch.empty((B, 0, self.model.class_n), device=self.device, dtype=torch.float32)
+        # slide the routing buffers: the last layer's next frame back to local lpad + 1
+        new_base = after[-1] - lpad - 1
+        if not finishing and new_base > base:
+            self._advance(new_base - base, after[1] - new_base)
+            self._base = new_base
+        n_valid = ((self._len_dev + 3) // 4 - t0).clamp_(0, m).to(torch.int32)
+        labels, count = self._greedy(logits, n_valid)
+        out = StreamOut(self, t0, logits)
+        self._pending.append((out, labels, count))
+        return out
