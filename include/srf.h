@@ -423,6 +423,40 @@ int srf_ctc_loss(const float* logits, const int* labels, const int* label_len, c
  * lowest class index wins (torch.argmax).  One wave per stream; any C >= 2, n >= 0. */
 int srf_ctc_greedy_n(const float* logits, const int* n_valid, int B, int n, int C, int blank, int* prev, int* labels,
                      int* count, void* stream);
+/* srf_ctc_beam_*: CTC prefix beam search on the device (tf.nn.ctc_beam_search_decoder
+ * with top_paths = 1 as process_test_step calls it; the algorithm of srf_ctc_beam_search
+ * in srf_data.h, which defines the result), batched and resumable: one workgroup per
+ * utterance, all frames of a chunk in one launch, the beam kept on the device between
+ * chunks.  1 <= beam_width <= SRF_CTC_BEAM_MAX_WIDTH, 2 <= C <= SRF_CTC_BEAM_MAX_CLASSES,
+ * 0 <= blank < C; anything else is refused.
+ *
+ * state: one opaque device block of srf_ctc_beam_state_bytes(B, C, beam_width,
+ * max_frames) bytes (4-byte aligned; 0 and a message if the shape is refused).  Per
+ * utterance it holds the beam (at most beam_width entries: trie node, log p(ends in
+ * blank), log p(ends in a label), last label, length, a 64-bit hash of the label
+ * sequence and of its parent's, by which a prefix finds its parent), the prefix trie as
+ * (parent, label) arrays of 1 + max_frames * beam_width nodes (a node is appended only
+ * for a prefix that survives a frame) and the frame count.  frames_pushed is a host
+ * counter the caller keeps with the block: reset zeroes it, push adds n to it.
+ *
+ * reset: every utterance back to the single empty prefix (pb = 0, pnb = -inf).
+ * push_n: logits [B][n][C], n_valid [B] (device); consumes the first clamp(n_valid[b], 0,
+ * n) frames of utterance b.  n = 0 is legal and launches nothing.  A push with
+ * *frames_pushed + n > max_frames is refused (SRF_EINVAL) and nothing runs.  The state
+ * after a frame depends on the state before it and the frame only, so any chunking of
+ * the same frames gives the same bits.
+ * best: the most probable prefix of each utterance: labels [B][max_frames] (the first
+ * count[b] are written), count [B], log_prob [B] = log(p_b + p_nb).  The state is not
+ * changed, so it may be called between pushes. */
+#define SRF_CTC_BEAM_MAX_WIDTH 128
+#define SRF_CTC_BEAM_MAX_CLASSES 128
+size_t srf_ctc_beam_state_bytes(int B, int C, int beam_width, int max_frames);
+int srf_ctc_beam_reset(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                       int* frames_pushed, void* stream);
+int srf_ctc_beam_push_n(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int blank,
+                        const float* logits, const int* n_valid, int n, int* frames_pushed, void* stream);
+int srf_ctc_beam_best(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int* labels,
+                      int* count, float* log_prob, void* stream);
 /* srf_stream_advance_n: up to SRF_STREAM_ADVANCE_MAX sliding state buffers, each
  * [B][rows_per_stream][row_bytes], move rows [shift, shift + keep) of every stream to
  * rows [0, keep) in one launch (the other rows keep or lose their content: undefined).

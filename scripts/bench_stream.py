@@ -10,7 +10,9 @@ and with the host clock around push() plus fetching the chunk's labels.  Next to
 offline forward of one session's audio, divided by the session's chunks.  One JSON line
 per configuration; no gate.
 
-    python scripts/bench_stream.py [--models c3_real c4_real] [--batch 1 8] [--chunk 32 64]
+    python scripts/bench_stream.py [--models c3_real c4_real] [--batch 1 8] [--chunk 32 64] [--beam W]
+
+--beam W adds the device beam search (StreamingRouter(beam_width=W)) to every timed chunk.
 """
 import argparse
 import json
@@ -75,6 +77,8 @@ def main():
     ap.add_argument('--chunks', type=int, default=50, help='chunks per session')
     ap.add_argument('--min-chunks', type=int, default=200, help='timed chunks per configuration, at least')
     ap.add_argument('--offline-reps', type=int, default=3)
+    ap.add_argument('--beam', type=int, default=None, metavar='W',
+                    help='also push every chunk through the device beam search of width W (in the timed chunk)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_stream.py needs a HIP device: chunk times are measured, never estimated')
@@ -89,7 +93,7 @@ def main():
             for chunk in args.chunk:
                 T = chunk * args.chunks
                 feats = torch.randn((B, T, sh.feat_dim), generator=torch.Generator().manual_seed(B * T)).to(dev)
-                s = StreamingRouter(model, B, max_chunk=chunk)
+                s = StreamingRouter(model, B, max_chunk=chunk, beam_width=args.beam)
                 timed_session(s, feats, chunk)   # warm-up: every shape the timed sessions use
                 dev_ms, host_ms, fin = [], [], []
                 while len(dev_ms) < args.min_chunks:
@@ -103,7 +107,8 @@ def main():
                 off = offline_ms(model, feats, args.offline_reps)
                 audio = chunk * FRAME_MS
                 row = {
-                    'model': name, 'B': B, 'chunk_frames': chunk, 'chunk_audio_ms': audio, 'timed_chunks': len(dev_ms),
+                    'model': name, 'B': B, 'beam': args.beam, 'chunk_frames': chunk, 'chunk_audio_ms': audio,
+                    'timed_chunks': len(dev_ms),
                     'chunk_ms_median': round(float(np.median(dev_ms)), 4),
                     'chunk_ms_p95': round(float(np.percentile(dev_ms, 95)), 4),
                     'chunk_host_ms_median': round(float(np.median(host_ms)), 4),

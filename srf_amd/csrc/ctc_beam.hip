@@ -1,0 +1,554 @@
+// CTC prefix beam search on the device: the algorithm of
+// csrc/data/ctc_beam.cpp, one workgroup per utterance, a whole chunk of frames per
+// launch, the beam kept in a device state block between launches.
+//
+// Per frame the host decoder walks the beam in slot order and creates, per slot k, the
+// prefix itself and then its extensions by ascending class; a prefix reached twice (a beam
+// entry that is the child (p, c) of another beam entry p) is one candidate whose two
+// contributions are added.  Here every candidate has the index of its first creation,
+//   key(k, itself) = k C,   key(k, extension c) = k C + 1 + (c < blank ? c : c - 1),
+// the merged candidate lives at the smaller of its two keys, and the beam_width
+// candidates that are largest by (total descending, key ascending) survive.  That is a
+// total order, so the result does not depend on which lane looks at which candidate.
+//
+// No table of all prefixes ever made: the beam holds distinct prefixes, so extension
+// (p, c) meets another candidate only if a beam entry n is the prefix p + c.  The host
+// knows that from its persistent (parent node, label) -> node map, in which a prefix that
+// left the beam and is made again (from its own parent, a frame or more later) gets its
+// old node back and so finds its children that stayed.  Trie nodes here are appended per
+// survivor and a prefix made again gets a new one, so node ids do not identify prefixes.
+// A 64-bit hash of the label sequence does (hash(p + c) = mix(hash(p), c), a pure
+// function of the prefix): every entry carries its own and its parent's, each frame
+// starts by finding every entry's parent slot (parent hash = hash and length = length - 1
+// over at most 128 x 128 pairs), and an entry marks its parent's extension in a
+// [slot][class] byte table.  Two different prefixes of one beam collide with probability
+// 2^-64 per pair.
+//
+// Candidate scores never go to memory: a lane computes prev + lp[c] for its (at most 32)
+// candidates once and keeps the ordered bits in registers.  A radix select (four 8-bit
+// passes over the ordered bits of the total, two more over the key if equal totals
+// straddle the edge of the beam) finds the threshold; the survivors (at most 128)
+// are ranked by counting and placed in rank order, new prefixes taking trie nodes in that
+// order, so the state after a frame is a pure function of the state before it and the
+// frame, whatever the chunking.
+#include "srf_common.h"
+#include "../../include/srf.h"
+
+namespace {
+
+constexpr int kThreads = 512;
+constexpr int kMaxW = SRF_CTC_BEAM_MAX_WIDTH;
+constexpr int kMaxC = SRF_CTC_BEAM_MAX_CLASSES;
+constexpr int kHeader = 4;   // state words per utterance before the beam: entries, trie nodes, frames, unused
+constexpr int kFields = 9;   // beam arrays: node, pb, pnb, last, len, hash (2 words), parent's hash (2 words)
+constexpr unsigned long long kRootHash = 0x243f6a8885a308d3ull;
+static_assert(kMaxW * kMaxC <= (1 << 14), "a candidate key takes 14 bits");
+constexpr int kPerLane = kMaxW * kMaxC / kThreads;   // candidates a lane looks at, at most
+static_assert(kThreads == 4 * kMaxW, "the ranking pass splits the survivors over four quarters of the workgroup");
+
+constexpr unsigned kKeyMax = (1u << 14) - 1;
+constexpr unsigned char kNoFold = 0xff;
+
+__host__ __device__ inline size_t trie_capacity(int W, int max_frames) { return 1 + (size_t)max_frames * W; }
+__host__ __device__ inline size_t state_words(int W, int max_frames) {
+  return kHeader + (size_t)kFields * W + 2 * trie_capacity(W, max_frames);
+}
+
+// hash of prefix + (c,) from the prefix's (the splitmix64 finaliser over hash ^ f(c))
+__device__ __forceinline__ unsigned long long extend_hash(unsigned long long h, int c) {
+  unsigned long long z = h ^ ((unsigned long long)(c + 1) * 0x9e3779b97f4a7c15ull);
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
+__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
+
+__device__ __forceinline__ float log_sum_exp(float a, float b) {
+  if (a == neg_inf()) return b;
+  if (b == neg_inf()) return a;
+  const float m = fmaxf(a, b);
+  return m + log1pf(expf(-fabsf(a - b)));
+}
+
+// Order-preserving map of a float onto unsigned (larger float, larger word), -0 as +0;
+// 0 is kept for "no candidate".
+__device__ __forceinline__ unsigned ordered(float f) {
+  unsigned b = __float_as_uint(f);
+  if ((b << 1) == 0) b = 0;
+  const unsigned u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return u == 0 ? 1u : u;
+}
+__device__ __forceinline__ float unordered(unsigned u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+struct alignas(16) Smem {
+  float lp[kMaxC];
+  // the beam, double-buffered over frames
+  int node[2][kMaxW];
+  float pb[2][kMaxW], pnb[2][kMaxW];
+  int last[2][kMaxW], len[2][kMaxW];
+  unsigned long long hash[2][kMaxW], phash[2][kMaxW];
+  int ps[kMaxW];        // slot of the entry's parent in the current beam, -1 if it is not there
+  // per slot, this frame
+  float tot[kMaxW], npb[kMaxW], npnb[kMaxW];
+  unsigned su[kMaxW];   // ordered total of the slot's own candidate
+  int alias[kMaxW];     // the key its own candidate lives at
+  int fidx[kMaxW];      // the extension it folded in (to clear the table), -1 if none
+  // survivors
+  unsigned long long sel[kMaxW];
+  int rank[kMaxW], extb[kMaxW];
+  unsigned hist[2][256];
+  unsigned char fold[kMaxW * kMaxC];   // [slot * C + j]: the beam entry that extension is, or kNoFold
+  int digit, above, eq, need, nsel, nadd;
+};
+
+struct Cand {
+  unsigned u;   // 0: no candidate at this key
+  int ext;      // 1: a new prefix (slot k extended by a class), 0: beam entry `slot` itself
+  int slot;
+};
+
+__device__ __forceinline__ int class_of(int j, int blank) { return j - 1 < blank ? j - 1 : j; }
+
+__device__ __forceinline__ Cand candidate(const Smem& s, int cur, int i, const FastDiv& divC, int C, int blank) {
+  const int k = (int)fdiv((unsigned)i, divC), j = i - k * C;
+  Cand r{0u, 0, k};
+  if (j == 0) {
+    if (s.alias[k] == i) r.u = s.su[k];
+    return r;
+  }
+  const unsigned char f = s.fold[i];
+  if (f != kNoFold) {
+    r.slot = f;
+    if (s.alias[f] == i) r.u = s.su[f];
+    return r;
+  }
+  const int c = class_of(j, blank);
+  const float prev = c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k];
+  if (prev == neg_inf()) return r;
+  r.u = ordered(prev + s.lp[c]);
+  r.ext = 1;
+  return r;
+}
+
+// Wave 0 after a histogram pass: the bin in which the need-th largest matching candidate
+// lies, how many lie in higher bins, and how many in that bin.  first: need is the beam
+// width capped by the number of candidates.
+__device__ __forceinline__ void pick_bin(Smem& s, const unsigned* h, int need, bool first, int W) {
+  const int lane = threadIdx.x;
+  const uint4 v = reinterpret_cast<const uint4*>(h)[lane];
+  const int b[4] = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
+  const int own = b[0] + b[1] + b[2] + b[3];
+  int suf = own;   // candidates in this lane's bins and higher ones
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_down(suf, o, 64);
+    if (lane + o < 64) suf += t;
+  }
+  const int total = __shfl(suf, 0, 64);
+  if (first) need = min(W, total);
+  int acc = suf - own;
+  if (acc < need && need <= suf) {
+#pragma unroll
+    for (int q = 3; q >= 0; --q) {
+      if (acc + b[q] >= need) {
+        s.digit = 4 * lane + q;
+        s.above = acc;
+        s.eq = b[q];
+        s.need = need;
+        break;
+      }
+      acc += b[q];
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __restrict__ state,
+                                                                 const float* __restrict__ logits,
+                                                                 const int* __restrict__ n_valid, int n, int C,
+                                                                 int blank, int W, int max_frames, FastDiv divC) {
+  __shared__ Smem s;
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int nv = max(0, min(n_valid[b], n));
+  if (nv == 0) return;
+  const size_t cap = trie_capacity(W, max_frames);
+  unsigned* st = state + (size_t)b * state_words(W, max_frames);
+  int* hdr = reinterpret_cast<int*>(st);
+  unsigned* beam = st + kHeader;
+  int* trie_parent = reinterpret_cast<int*>(beam + (size_t)kFields * W);
+  int* trie_label = trie_parent + cap;
+  const float* x = logits + (size_t)b * n * C;
+
+  int nb = min(max(hdr[0], 1), W), n_nodes = hdr[1];
+  int cur = 0;
+  if (t < nb) {
+    s.node[0][t] = (int)beam[t];
+    s.pb[0][t] = __uint_as_float(beam[W + t]);
+    s.pnb[0][t] = __uint_as_float(beam[2 * W + t]);
+    // (the clamp keeps a block that was never reset from indexing outside the tables)
+    const int last = (int)beam[3 * W + t];
+    s.last[0][t] = last >= C || last == blank ? -1 : max(last, -1);
+    s.len[0][t] = (int)beam[4 * W + t];
+    s.hash[0][t] = (unsigned long long)beam[6 * W + t] << 32 | beam[5 * W + t];
+    s.phash[0][t] = (unsigned long long)beam[8 * W + t] << 32 | beam[7 * W + t];
+  }
+  if (t < kMaxW) s.ps[t] = -1;
+  for (int i = t; i < kMaxW * kMaxC / 4; i += kThreads) reinterpret_cast<unsigned*>(s.fold)[i] = 0xffffffffu;
+  if (t < 256) s.hist[0][t] = s.hist[1][t] = 0;
+
+  __syncthreads();
+
+  // wave 0 loads a frame's logits (classes lane and lane + 64) at the start of the frame before
+  float xa = neg_inf(), xb = neg_inf();
+  if (t < 64) {
+    if (t < C) xa = x[t];
+    if (t + 64 < C) xb = x[t + 64];
+  }
+
+  for (int f = 0; f < nv; ++f) {
+    // ---- every entry's parent slot: the entry one label shorter whose hash is its parent's
+    {
+      const int me = t & (kMaxW - 1), q = t / kMaxW;
+      if (me < nb && s.last[cur][me] >= 0) {
+        const unsigned long long want = s.phash[cur][me];
+        const int want_len = s.len[cur][me] - 1;
+        const int hi = min(nb, (q + 1) * (kMaxW / 4));
+        for (int k = q * (kMaxW / 4); k < hi; ++k)
+          if (s.hash[cur][k] == want && s.len[cur][k] == want_len) s.ps[me] = k;
+      }
+    }
+    // ---- log-softmax of the frame
+    if (t < 64) {
+      const float a = xa, c = xb;
+      if (f + 1 < nv) {
+        const float* row = x + (size_t)(f + 1) * C;
+        if (t < C) xa = row[t];
+        if (t + 64 < C) xb = row[t + 64];
+      }
+      float mx = fmaxf(a, c);
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      const float se = wave_sum((t < C ? expf(a - mx) : 0.f) + (t + 64 < C ? expf(c - mx) : 0.f));
+      const float norm = mx + logf(se);
+      if (t < C) s.lp[t] = a - norm;
+      if (t + 64 < C) s.lp[t + 64] = c - norm;
+    }
+    __syncthreads();
+
+    // ---- per beam slot: its own candidate, with its parent's extension folded in
+    if (t < kMaxW) {
+      s.rank[t] = 0;
+      s.extb[t] = 0;
+    }
+    if (t == 0) s.nsel = 0;
+    if (t < nb) {
+      const float pb = s.pb[cur][t], pnb = s.pnb[cur][t];
+      const int last = s.last[cur][t], ps = s.ps[t];
+      const float tot = log_sum_exp(pb, pnb);
+      float npnb = last >= 0 ? pnb + s.lp[last] : neg_inf();
+      int alias = t * C, fidx = -1;
+      if (ps >= 0) {
+        const float ppb = s.pb[cur][ps];
+        const float prev = last == s.last[cur][ps] ? ppb : log_sum_exp(ppb, s.pnb[cur][ps]);
+        if (prev != neg_inf()) {
+          npnb = log_sum_exp(npnb, prev + s.lp[last]);
+          fidx = ps * C + 1 + (last < blank ? last : last - 1);
+          s.fold[fidx] = (unsigned char)t;
+          alias = min(alias, fidx);
+        }
+      }
+      const float npb = tot + s.lp[blank];
+      s.tot[t] = tot;
+      s.npb[t] = npb;
+      s.npnb[t] = npnb;
+      s.su[t] = ordered(log_sum_exp(npb, npnb));
+      s.alias[t] = alias;
+      s.fidx[t] = fidx;
+    }
+    __syncthreads();
+
+    // ---- radix select: the need-th largest (ordered total, kKeyMax - key)
+    // Each lane keeps the ordered totals of its candidates (keys t, t + kThreads, ...) in
+    // registers for all passes.  Totals of one frame share their leading bits, so a lane
+    // counts runs of equal digits and adds each run to the histogram once.
+    const int ncand = nb * C;
+    unsigned uc[kPerLane];
+#pragma unroll
+    for (int m = 0; m < kPerLane; ++m) {
+      const int i = m * kThreads + t;
+      uc[m] = i < ncand ? candidate(s, cur, i, divC, C, blank).u : 0u;
+    }
+    unsigned V = 0, Lthr = 0;
+    int need = 0, eq = 0;
+    for (int p = 0; p < 6; ++p) {
+      const bool on_key = p >= 4;
+      const int shift = on_key ? 8 * (5 - p) : 8 * (3 - p);
+      unsigned* h = s.hist[p & 1];
+      if (t < 256) s.hist[(p + 1) & 1][t] = 0;
+      unsigned run_digit = 0, run = 0;
+#pragma unroll
+      for (int m = 0; m < kPerLane; ++m) {
+        if (m * kThreads >= ncand) break;
+        const unsigned u = uc[m];
+        if (u == 0) continue;
+        unsigned digit;
+        if (!on_key) {
+          if (p != 0 && (u >> (shift + 8)) != (V >> (shift + 8))) continue;
+          digit = (u >> shift) & 255u;
+        } else {
+          if (u != V) continue;
+          const unsigned lo = kKeyMax - (unsigned)(m * kThreads + t);
+          if (p != 4 && (lo >> 8) != (Lthr >> 8)) continue;
+          digit = (lo >> shift) & 255u;
+        }
+        if (digit != run_digit) {
+          if (run) atomicAdd(&h[run_digit], run);
+          run_digit = digit;
+          run = 0;
+        }
+        ++run;
+      }
+      if (run) atomicAdd(&h[run_digit], run);
+      __syncthreads();
+      if (t < 64) pick_bin(s, h, need, p == 0, W);
+      __syncthreads();
+      need = s.need - s.above;
+      eq = s.eq;
+      if (on_key)
+        Lthr |= (unsigned)s.digit << shift;
+      else
+        V |= (unsigned)s.digit << shift;
+      // after the fourth pass V is the threshold total: eq candidates have it, need of
+      // them survive.  All of them: done; else the two passes over the key choose.
+      // (hist[0] was cleared during the fourth pass, as it is during the sixth)
+      if (p == 3 && eq == need) break;
+    }
+
+    // ---- the survivors, in any order
+#pragma unroll
+    for (int m = 0; m < kPerLane; ++m) {
+      if (m * kThreads >= ncand) break;
+      const unsigned u = uc[m];
+      if (u == 0) continue;
+      const int i = m * kThreads + t;
+      const unsigned lo = kKeyMax - (unsigned)i;
+      if (u > V || (u == V && lo >= Lthr)) {
+        const int ext = candidate(s, cur, i, divC, C, blank).ext;
+        const int at = atomicAdd(&s.nsel, 1);
+        if (at < kMaxW) s.sel[at] = (unsigned long long)u << 32 | (lo << 1) | (unsigned)ext;
+      }
+    }
+    __syncthreads();
+    const int nsel = min(s.nsel, W);
+
+    // ---- rank of each survivor, and how many new prefixes precede it
+    {
+      const int me = t & (kMaxW - 1), q = t / kMaxW;
+      if (me < nsel) {
+        const unsigned long long mine = s.sel[me];
+        int r = 0, e = 0;
+        const int hi = min(nsel, (q + 1) * (kMaxW / 4));
+        for (int o = q * (kMaxW / 4); o < hi; ++o) {
+          const unsigned long long other = s.sel[o];
+          if (other > mine) {
+            ++r;
+            e += (int)(other & 1u);
+          }
+        }
+        if (r) atomicAdd(&s.rank[me], r);
+        if (e) atomicAdd(&s.extb[me], e);
+      }
+    }
+    __syncthreads();
+
+    // ---- place them: the next beam, in rank order
+    const int nxt = cur ^ 1;
+    if (t < kMaxW) s.ps[t] = -1;
+    if (t < nsel) {
+      const unsigned long long mine = s.sel[t];
+      const int r = s.rank[t], ext = (int)(mine & 1u);
+      const int i = (int)(kKeyMax - ((unsigned)mine >> 1));
+      const int k = (int)fdiv((unsigned)i, divC), j = i - k * C;
+      if (!ext) {
+        const int from = j == 0 ? k : (int)s.fold[i];
+        s.node[nxt][r] = s.node[cur][from];
+        s.pb[nxt][r] = s.npb[from];
+        s.pnb[nxt][r] = s.npnb[from];
+        s.last[nxt][r] = s.last[cur][from];
+        s.len[nxt][r] = s.len[cur][from];
+        s.hash[nxt][r] = s.hash[cur][from];
+        s.phash[nxt][r] = s.phash[cur][from];
+      } else {
+        const int c = class_of(j, blank);
+        const size_t id = (size_t)n_nodes + s.extb[t];
+        if (id < cap) {   // holds while the frames pushed stay within max_frames (checked on the host)
+          trie_parent[id] = s.node[cur][k];
+          trie_label[id] = c;
+        }
+        s.node[nxt][r] = (int)id;
+        s.pb[nxt][r] = neg_inf();
+        s.pnb[nxt][r] = unordered((unsigned)(mine >> 32));
+        s.last[nxt][r] = c;
+        s.len[nxt][r] = s.len[cur][k] + 1;
+        s.hash[nxt][r] = extend_hash(s.hash[cur][k], c);
+        s.phash[nxt][r] = s.hash[cur][k];
+      }
+      if (r == nsel - 1) s.nadd = s.extb[t] + ext;
+    }
+    __syncthreads();
+
+    // ---- the fold table back to empty (it is written again after the next frame's first barrier)
+    if (t < nb && s.fidx[t] >= 0) s.fold[s.fidx[t]] = kNoFold;
+    n_nodes += s.nadd;
+    nb = nsel;
+    cur = nxt;
+  }
+  if (t < nb) {
+    beam[t] = (unsigned)s.node[cur][t];
+    beam[W + t] = __float_as_uint(s.pb[cur][t]);
+    beam[2 * W + t] = __float_as_uint(s.pnb[cur][t]);
+    beam[3 * W + t] = (unsigned)s.last[cur][t];
+    beam[4 * W + t] = (unsigned)s.len[cur][t];
+    beam[5 * W + t] = (unsigned)s.hash[cur][t];
+    beam[6 * W + t] = (unsigned)(s.hash[cur][t] >> 32);
+    beam[7 * W + t] = (unsigned)s.phash[cur][t];
+    beam[8 * W + t] = (unsigned)(s.phash[cur][t] >> 32);
+  }
+  if (t == 0) {
+    hdr[0] = nb;
+    hdr[1] = n_nodes;
+    hdr[2] += nv;
+  }
+}
+
+__global__ __launch_bounds__(64) void ctc_beam_reset_kernel(unsigned* __restrict__ state, int W, int max_frames) {
+  if (threadIdx.x != 0) return;
+  unsigned* st = state + (size_t)blockIdx.x * state_words(W, max_frames);
+  int* hdr = reinterpret_cast<int*>(st);
+  unsigned* beam = st + kHeader;
+  int* trie_parent = reinterpret_cast<int*>(beam + (size_t)kFields * W);
+  hdr[0] = 1;
+  hdr[1] = 1;
+  hdr[2] = 0;
+  hdr[3] = 0;
+  beam[0] = 0;                                // the root: the empty prefix
+  beam[W] = __float_as_uint(0.f);             // pb
+  beam[2 * W] = __float_as_uint(neg_inf());   // pnb
+  beam[3 * W] = (unsigned)-1;                 // no last label
+  beam[4 * W] = 0;                            // length
+  beam[5 * W] = (unsigned)kRootHash;
+  beam[6 * W] = (unsigned)(kRootHash >> 32);
+  beam[7 * W] = beam[8 * W] = 0;              // no parent
+  trie_parent[0] = -1;
+  trie_parent[trie_capacity(W, max_frames)] = -1;   // label of the root
+}
+
+// One wave per utterance.  The first slot with the largest total (after a frame the beam
+// is in rank order, so slot 0); lane 0 walks the trie from its node to the root.
+__global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __restrict__ state, int W, int max_frames,
+                                                           int* __restrict__ labels, int* __restrict__ count,
+                                                           float* __restrict__ log_prob) {
+  if (threadIdx.x != 0) return;
+  const int b = blockIdx.x;
+  const size_t cap = trie_capacity(W, max_frames);
+  const unsigned* st = state + (size_t)b * state_words(W, max_frames);
+  const int* hdr = reinterpret_cast<const int*>(st);
+  const unsigned* beam = st + kHeader;
+  const int* trie_parent = reinterpret_cast<const int*>(beam + (size_t)kFields * W);
+  const int* trie_label = trie_parent + cap;
+  const int nb = min(max(hdr[0], 1), W);
+  int best = 0;
+  float best_tot = log_sum_exp(__uint_as_float(beam[W]), __uint_as_float(beam[2 * W]));
+  for (int k = 1; k < nb; ++k) {
+    const float tot = log_sum_exp(__uint_as_float(beam[W + k]), __uint_as_float(beam[2 * W + k]));
+    if (tot > best_tot) {
+      best = k;
+      best_tot = tot;
+    }
+  }
+  const int len = min(max((int)beam[4 * W + best], 0), max_frames);
+  int* out = labels + (size_t)b * max_frames;
+  int node = (int)beam[best];
+  for (int i = len - 1; i >= 0 && node > 0 && (size_t)node < cap; --i) {
+    out[i] = trie_label[node];
+    node = trie_parent[node];
+  }
+  count[b] = len;
+  log_prob[b] = best_tot;
+}
+
+bool shape_ok(int B, int C, int W, int max_frames) {
+  return B >= 1 && C >= 2 && C <= kMaxC && W >= 1 && W <= kMaxW && max_frames >= 1 &&
+         state_words(W, max_frames) <= (size_t)0x7fffffff;
+}
+
+}  // namespace
+
+#define SRF_BEAM_SHAPE(what)                                                                                          \
+  SRF_REQUIRE(shape_ok(B, C, beam_width, max_frames),                                                                 \
+              what ": need B >= 1, 2 <= C <= %d, 1 <= beam_width <= %d, max_frames >= 1 and a trie below 2^31 "       \
+                   "words (B=%d C=%d beam_width=%d max_frames=%d)",                                                   \
+              kMaxC, kMaxW, B, C, beam_width, max_frames)
+
+#define SRF_BEAM_STATE(what)                                                                                          \
+  do {                                                                                                                \
+    SRF_BEAM_SHAPE(what);                                                                                             \
+    SRF_REQUIRE(state && frames_pushed, what ": null state / frames_pushed");                                         \
+    SRF_REQUIRE(state_bytes >= (size_t)B * state_words(beam_width, max_frames) * 4,                                   \
+                what ": the state block holds %zu bytes, %zu are needed", state_bytes,                                \
+                (size_t)B * state_words(beam_width, max_frames) * 4);                                                 \
+  } while (0)
+
+extern "C" size_t srf_ctc_beam_state_bytes(int B, int C, int beam_width, int max_frames) {
+  if (!shape_ok(B, C, beam_width, max_frames)) {
+    srf::set_error("ctc_beam_state_bytes: need B >= 1, 2 <= C <= %d, 1 <= beam_width <= %d, max_frames >= 1 and a "
+                   "trie below 2^31 words (B=%d C=%d beam_width=%d max_frames=%d)",
+                   kMaxC, kMaxW, B, C, beam_width, max_frames);
+    return 0;
+  }
+  return (size_t)B * state_words(beam_width, max_frames) * 4;
+}
+
+extern "C" int srf_ctc_beam_reset(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                  int* frames_pushed, void* stream) {
+  SRF_BEAM_STATE("ctc_beam_reset");
+  hipLaunchKernelGGL(ctc_beam_reset_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned*>(state), beam_width, max_frames);
+  SRF_LAUNCH_CHECK("ctc_beam_reset");
+  *frames_pushed = 0;
+  return SRF_OK;
+}
+
+extern "C" int srf_ctc_beam_push_n(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                   int blank, const float* logits, const int* n_valid, int n, int* frames_pushed,
+                                   void* stream) {
+  SRF_BEAM_STATE("ctc_beam_push");
+  SRF_REQUIRE(blank >= 0 && blank < C, "ctc_beam_push: blank = %d outside [0, %d)", blank, C);
+  SRF_REQUIRE(n >= 0 && n_valid, "ctc_beam_push: need n >= 0 and n_valid (n=%d)", n);
+  SRF_REQUIRE(n == 0 || logits, "ctc_beam_push: null logits with n = %d", n);
+  SRF_REQUIRE(*frames_pushed >= 0 && (long long)*frames_pushed + n <= max_frames,
+              "ctc_beam_push: %d frames after %d pushed since the reset exceed max_frames = %d", n, *frames_pushed,
+              max_frames);
+  if (n == 0) return SRF_OK;
+  hipLaunchKernelGGL(ctc_beam_push_kernel, dim3((unsigned)B), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned*>(state), logits, n_valid, n, C, blank, beam_width, max_frames,
+                     make_fastdiv((unsigned)C));
+  SRF_LAUNCH_CHECK("ctc_beam_push");
+  *frames_pushed += n;
+  return SRF_OK;
+}
+
+extern "C" int srf_ctc_beam_best(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                 int* labels, int* count, float* log_prob, void* stream) {
+  SRF_BEAM_SHAPE("ctc_beam_best");
+  SRF_REQUIRE(state && labels && count && log_prob, "ctc_beam_best: null pointer argument");
+  SRF_REQUIRE(state_bytes >= (size_t)B * state_words(beam_width, max_frames) * 4,
+              "ctc_beam_best: the state block holds %zu bytes, %zu are needed", state_bytes,
+              (size_t)B * state_words(beam_width, max_frames) * 4);
+  hipLaunchKernelGGL(ctc_beam_best_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned*>(state), beam_width, max_frames, labels, count, log_prob);
+  SRF_LAUNCH_CHECK("ctc_beam_best");
+  return SRF_OK;
+}

@@ -53,6 +53,80 @@ def greedy_decode_device(logits, n_valid, blank_index, prev):
     return ops.ctc_greedy_chunk(logits.contiguous(), n_valid, blank_index, prev)
 
 
+BEAM_MAX_WIDTH = 128     # SRF_CTC_BEAM_MAX_WIDTH
+BEAM_MAX_CLASSES = 128   # SRF_CTC_BEAM_MAX_CLASSES
+
+
+def _check_beam_range(n_classes, blank_index, beam_width):
+    if not 2 <= int(n_classes) <= BEAM_MAX_CLASSES:
+        raise ValueError(f'the device beam search takes 2 .. {BEAM_MAX_CLASSES} classes, got {n_classes}')
+    if not 1 <= int(beam_width) <= BEAM_MAX_WIDTH:
+        raise ValueError(f'the device beam search takes a beam width of 1 .. {BEAM_MAX_WIDTH}, got {beam_width}')
+    if not 0 <= int(blank_index) < int(n_classes):
+        raise ValueError(f'blank index {blank_index} outside [0, {n_classes})')
+
+
+class BeamState:
+    """Resumable CTC prefix beam search on the device (srf_ctc_beam_*): the beams of
+    ``n_utts`` utterances, kept in one device block between chunks.
+
+    ``push(logits [B, n, C], n_valid [B])`` extends utterance b's beam by the first
+    n_valid[b] frames of the chunk (one launch for the whole chunk); ``best()`` returns
+    (list of label lists, numpy log probabilities) of the most probable prefixes so far
+    and leaves the state as it is; ``reset()`` starts over.  At most ``max_frames``
+    frames may be pushed between two resets.  The result is that of beam_search_decode
+    on the frames pushed, however they were cut into chunks."""
+
+    def __init__(self, n_utts, n_classes, blank_index, beam_width=100, max_frames=4096, device='cuda'):
+        _check_beam_range(n_classes, blank_index, beam_width)
+        if int(n_utts) < 1 or int(max_frames) < 1:
+            raise ValueError(f'need n_utts >= 1 and max_frames >= 1, got {n_utts} and {max_frames}')
+        self.shape = (int(n_utts), int(n_classes), int(beam_width), int(max_frames))
+        self.blank = int(blank_index)
+        self.device = torch.device(device)
+        self._pushed = ctypes.c_int(0)
+        self._state = torch.empty(ops.ctc_beam_state_bytes(*self.shape), device=self.device, dtype=torch.uint8)
+        self.reset()
+
+    @property
+    def frames_pushed(self):
+        return self._pushed.value
+
+    def reset(self):
+        ops.ctc_beam_reset(self._state, self.shape, self._pushed)
+
+    def push(self, logits, n_valid):
+        n_valid = torch.as_tensor(n_valid).to(device=self.device, dtype=torch.int32).contiguous()
+        ops.ctc_beam_push(self._state, self.shape, self._pushed, logits.detach().float().contiguous(), n_valid,
+                          self.blank)
+
+    def best_device(self):
+        """(labels [B, max_frames] int32, count [B] int32, log_prob [B] float32), on the device."""
+        return ops.ctc_beam_best(self._state, self.shape)
+
+    def best(self):
+        labels, count, log_prob = self.best_device()
+        count = count.cpu().tolist()
+        labels = labels[:, :max(count + [1])].cpu().tolist()
+        return [labels[b][:count[b]] for b in range(self.shape[0])], log_prob.cpu().double().numpy()
+
+
+def beam_search_decode_device(logits, lengths, blank_index, beam_width=100):
+    """beam_search_decode on the device: one reset, one push and one best call of the HIP
+    prefix beam search; the labels, counts and scores are copied to the host, the logits
+    are not.  logits [B, T, C] on the device, 2 <= C <= 128, 1 <= beam_width <= 128
+    (ValueError otherwise); returns (list of label lists, numpy log probabilities)."""
+    if logits.dim() != 3 or not logits.is_cuda:
+        raise ValueError(f'logits must be a device tensor [B, T, C], got {tuple(logits.shape)} on {logits.device}')
+    B, T, C = logits.shape
+    _check_beam_range(C, blank_index, beam_width)
+    if B < 1:
+        raise ValueError('logits hold no utterance')
+    state = BeamState(B, C, blank_index, beam_width, max(T, 1), logits.device)
+    state.push(logits, torch.as_tensor(lengths))
+    return state.best()
+
+
 def beam_search_decode(logits, lengths, blank_index, beam_width=100):
     """tf.nn.ctc_beam_search_decoder(time-major logits, lengths, beam_width,
     top_paths=1) as process_test_step calls it (trainer_sr.py:109-112), on the host

@@ -570,6 +570,56 @@ def ctc_greedy_chunk(logits, n_valid, blank, prev):
     return labels, count
 
 
+def ctc_beam_state_bytes(B, C, beam_width, max_frames):
+    """srf_ctc_beam_state_bytes; raises SrfError (with the library's message) for a
+    shape the device beam search refuses."""
+    L = _lib.lib()
+    n = L.srf_ctc_beam_state_bytes(int(B), int(C), int(beam_width), int(max_frames))
+    if n == 0:
+        _lib.check(-1, 'srf_ctc_beam_state_bytes')
+    return n
+
+
+def _beam_state_args(state, shape):
+    if not state.is_cuda or state.dtype != torch.uint8 or not state.is_contiguous():
+        raise ValueError('the beam state must be a contiguous uint8 device tensor')
+    B, C, W, max_frames = shape
+    return _ptr(state), state.numel(), int(B), int(C), int(W), int(max_frames)
+
+
+def ctc_beam_reset(state, shape, frames_pushed):
+    """srf_ctc_beam_reset on the state block of shape = (B, C, beam_width, max_frames);
+    frames_pushed: the ctypes.c_int host counter kept with the block."""
+    _lib.check(_lib.lib().srf_ctc_beam_reset(*_beam_state_args(state, shape), ctypes.byref(frames_pushed), _stream()),
+               'srf_ctc_beam_reset')
+
+
+def ctc_beam_push(state, shape, frames_pushed, logits, n_valid, blank):
+    """srf_ctc_beam_push_n: the first n_valid[b] frames of logits [B, n, C] extend
+    utterance b's beam."""
+    B, C = shape[0], shape[1]
+    n = logits.shape[1] if logits.dim() == 3 else -1
+    _check_dev('logits', logits, (B, n, C))
+    t = n_valid
+    if not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+        raise ValueError(f'n_valid must be a contiguous int32 device tensor of shape ({B},)')
+    args = _beam_state_args(state, shape)
+    _lib.check(_lib.lib().srf_ctc_beam_push_n(*args, int(blank), _ptr(logits), _ptr(n_valid), n,
+                                              ctypes.byref(frames_pushed), _stream()), 'srf_ctc_beam_push_n')
+
+
+def ctc_beam_best(state, shape):
+    """srf_ctc_beam_best: (labels [B, max_frames] int32, count [B] int32, log_prob [B]
+    float32) on the device; the state is left as it is."""
+    B, max_frames = shape[0], shape[3]
+    labels = torch.empty((B, max_frames), device=state.device, dtype=torch.int32)
+    count = torch.empty(B, device=state.device, dtype=torch.int32)
+    log_prob = torch.empty(B, device=state.device, dtype=torch.float32)
+    _lib.check(_lib.lib().srf_ctc_beam_best(*_beam_state_args(state, shape), _ptr(labels), _ptr(count), _ptr(log_prob),
+                                            _stream()), 'srf_ctc_beam_best')
+    return labels, count, log_prob
+
+
 def stream_advance(bufs):
     """srf_stream_advance_n: bufs = [(tensor [B, rows, ...], rows, shift, keep)]; rows
     [shift, shift + keep) of every stream of every tensor move to rows [0, keep), in

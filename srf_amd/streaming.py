@@ -105,9 +105,12 @@ class StreamingRouter:
 
     ``push(feats, ended=None)`` / ``finish()`` return a ``StreamOut``; ``reset()`` starts
     over; ``lookahead`` is 2 + L * rpad output frames; ``hypotheses`` the greedy labels so
-    far.  The model's parameters and BatchNorm moving statistics are read, never written."""
+    far.  With ``beam_width`` (1 .. 128) every chunk's logits also extend a device beam
+    search (ctc.BeamState, at most ``max_frames`` output frames per stream, 4096 by
+    default): ``beam_hypotheses`` and ``beam_scores`` are its result so far.  The model's
+    parameters and BatchNorm moving statistics are read, never written."""
 
-    def __init__(self, model, n_streams, max_chunk=64):
+    def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None):
         if model.caps_type == 'einsum':
             raise ValueError('the einsum variant cannot stream: its positional encoding needs the absolute frame '
                              'index, which srf_primary_caps_fwd_ex does not take')
@@ -127,6 +130,12 @@ class StreamingRouter:
         # primary-capsule frame is at most max_chunk / 4 + L * rpad frames ahead of D
         # (2 + L * rpad at finish), and an SDR pose at finish reads rpad zero frames more
         self.cap = self.max_chunk // 4 + (self.L + 1) * self.rpad + self.lpad + 3
+        # with a beam width: the device prefix beam search next to the greedy decoder, its
+        # beams carried from chunk to chunk (at most max_frames output frames per stream)
+        self._beam = None
+        if beam_width:
+            self._beam = ctc.BeamState(self.B, model.class_n, self.blank, beam_width,
+                                       4096 if max_frames is None else max_frames, self.device)
         self._alloc()
         self.reset()
 
@@ -165,6 +174,27 @@ class StreamingRouter:
         self._finished = False
         self._hyp = [[] for _ in range(self.B)]
         self._pending = []      # (StreamOut, labels, count) not yet fetched from the device
+        if self._beam is not None:
+            self._beam.reset()
+        self._beam_best = None  # (labels, scores) of the frames pushed so far, once fetched
+
+    def _fetch_beam(self):
+        if self._beam is None:
+            raise ValueError('this router decodes greedily only: build it with a beam_width')
+        if self._beam_best is None:
+            self._beam_best = self._beam.best()
+        return self._beam_best
+
+    @property
+    def beam_hypotheses(self):
+        """Per stream, the beam search's most probable labelling of the frames emitted so
+        far (beam_search_decode at the width given; fetched from the device on first use)."""
+        return [list(h) for h in self._fetch_beam()[0]]
+
+    @property
+    def beam_scores(self):
+        """Per stream, the log probability of its beam hypothesis (numpy)."""
+        return self._fetch_beam()[1].copy()
 
     @property
     def hypotheses(self):
@@ -259,6 +289,7 @@ class StreamingRouter:
             raise ValueError(f'a chunk holds a multiple of 4 input frames, at most max_chunk = {self.max_chunk}; '
                              f'got {n}')
         lengths = check_ended(self._lengths, ended, self._pushed, n)
+        self._check_beam_room(n, False)
         if lengths != self._lengths:
             self._lengths = lengths
             self._len_dev.copy_(torch.tensor([_NO_END if e is None else e for e in lengths], dtype=torch.int32))
@@ -270,10 +301,22 @@ class StreamingRouter:
         that never declared a length ends with the last pushed frame."""
         if self._finished:
             raise ValueError('finish() was already called: call reset() to start new utterances')
+        self._check_beam_room(0, True)
         with torch.no_grad():
             out = self._step(None, True)
         self._finished = True
         return out
+
+    def _check_beam_room(self, n, finishing):
+        """Refuse a step whose output frames the beam search cannot take, before anything
+        advances: the router stays as it was, its hypotheses so far can be read, and
+        reset() starts over."""
+        if self._beam is None:
+            return
+        emitted = frames_final(self._pushed + n, self.L, self.rpad, finished=finishing)[-1]
+        if emitted > self._beam.shape[3]:
+            raise ValueError(f'this step would bring the output frames to {emitted}, beyond the beam search\'s '
+                             f'max_frames = {self._beam.shape[3]}: build the router with a larger max_frames')
 
     def _step(self, feats, finishing):
         B, lpad, rpad = self.B, self.lpad, self.rpad
@@ -332,6 +375,9 @@ class StreamingRouter:
             self._base = new_base
         n_valid = ((self._len_dev + 3) // 4 - t0).clamp_(0, m).to(torch.int32)
         labels, count = self._greedy(logits, n_valid)
+        if self._beam is not None:
+            self._beam.push(logits, n_valid)
+            self._beam_best = None
         out = StreamOut(self, t0, logits)
         self._pending.append((out, labels, count))
         return out

@@ -617,16 +617,21 @@ def process_valid_step(in_len_div, inputs, model, loss_state, blank_idx):
 
 
 @torch.no_grad()
-def process_test_step(in_len_div, inputs, model, beam_width=None):
+def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'):
     """trainer_sr.py:96-117: forward, then tf.nn.ctc_beam_search_decoder(beam_width,
-    top_paths=1) on the host (srf_amd.ctc.beam_search_decode); best-path decoding
-    when no beam width is configured.  Decode lengths use floor division, as the
-    reference does (:110)."""
+    top_paths=1) on the host (srf_amd.ctc.beam_search_decode) or, with
+    decoder='device', on the GPU (srf_amd.ctc.beam_search_decode_device); best-path
+    decoding when no beam width is configured.  Decode lengths use floor division, as
+    the reference does (:110)."""
+    if decoder not in ('host', 'device'):
+        raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
     feats, _, inp_len, _, utt_id = inputs
     feats = _crop(feats, inp_len)
     y_pred = model(feats, input_lengths=inp_len, training=False)
     lens = inp_len.to(torch.int64) // in_len_div
-    if beam_width:
+    if beam_width and decoder == 'device':
+        hyps, _ = ctc.beam_search_decode_device(y_pred, lens, y_pred.shape[-1] - 1, beam_width)
+    elif beam_width:
         hyps, _ = ctc.beam_search_decode(y_pred, lens, y_pred.shape[-1] - 1, beam_width)
     else:
         hyps = ctc.greedy_decode(y_pred, lens, y_pred.shape[-1] - 1)
