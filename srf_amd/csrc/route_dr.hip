@@ -18,6 +18,7 @@
 // bias [in_n][J*Dout]; per-frame vectors [F][J*Dout].
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "srf_common.h"
 #include "route_fwd32.h"
@@ -37,13 +38,7 @@ thread_local int t_ev_n = 0;
 constexpr int MODE_FWD = 0;
 constexpr int MODE_BWD = 1;
 
-struct Geom {
-  int B, T, N, din, lpad, rpad, J, dout, iters, mask_first;
-  int F() const { return B * T; }
-  int in_n() const { return N * (lpad + rpad + 1); }
-  int JD() const { return J * dout; }
-  int NT() const { return (J * dout + 15) / 16; }
-};
+using srf::DrGeom;   // the layer geometry (route_fwd32.h)
 
 // ---------------------------------------------------------------- fragments
 // MFMA operand k-permutation: k-step ks of lane group g carries input element
@@ -1957,7 +1952,7 @@ struct PassCfg {
   int TW, NW;
 };
 
-PassCfg pass_cfg(const Geom& g) {
+PassCfg pass_cfg(const DrGeom& g) {
   const int NT = g.NT();
   int TW = 8;
   int NW = (NT + TW - 1) / TW;
@@ -1971,7 +1966,7 @@ PassCfg pass_cfg(const Geom& g) {
 // Pick the i-chunk count: minimise (scheduling rounds x capsules per workgroup)
 // given the workgroups that fit on 256 CUs, preferring chunk counts that divide
 // 8 (one i-chunk of W per XCD L2) and fewer slabs.
-int auto_chunks(const Geom& g, int NW) {
+int auto_chunks(const DrGeom& g, int NW) {
   const int n_ftiles = (g.F() + 15) / 16;
   const int wg_per_cu = std::max(1, 8 / NW);   // ~2 waves per SIMD at our register budget
   const int slots = 256 * wg_per_cu;
@@ -1991,18 +1986,8 @@ int auto_chunks(const Geom& g, int NW) {
   return best;
 }
 
-int check_geom(const Geom& g) {
-  SRF_REQUIRE(g.B > 0 && g.T > 0 && g.N > 0 && g.J > 1, "bad shape B=%d T=%d N=%d J=%d", g.B, g.T, g.N, g.J);
-  SRF_REQUIRE(g.lpad >= 0 && g.rpad >= 0, "negative window pad");
-  SRF_REQUIRE(g.iters >= 1 && g.iters <= 5, "routing iterations must be in [1,5], got %d", g.iters);
-  SRF_REQUIRE(g.din == 8 || g.din == 16 || g.din == 32 || g.din == 64, "unsupported in_d %d", g.din);
-  SRF_REQUIRE(g.dout == g.din, "in_d (%d) != out_d (%d) is not supported", g.din, g.dout);
-  SRF_REQUIRE((long long)g.F() * g.in_n() * g.JD() < (1LL << 40), "problem too large");
-  return SRF_OK;
-}
-
 template <int D, int TW, int MODE>
-void launch_pass(const Geom& g, int NW, int n_chunks, const float* emb, const float* W, const float* bias, int r,
+void launch_pass(const DrGeom& g, int NW, int n_chunks, const float* emb, const float* W, const float* bias, int r,
                  const float* vc, const float* gsv, float* slab, float* stats, int want_acc, hipStream_t st) {
   const int n_ftiles = (g.F() + 15) / 16;
   const int chunk_len = (g.in_n() + n_chunks - 1) / n_chunks;
@@ -2014,7 +1999,7 @@ void launch_pass(const Geom& g, int NW, int n_chunks, const float* emb, const fl
 }
 
 template <int D, int MODE>
-void dispatch_pass(const Geom& g, const PassCfg& pc, int n_chunks, const float* emb, const float* W,
+void dispatch_pass(const DrGeom& g, const PassCfg& pc, int n_chunks, const float* emb, const float* W,
                    const float* bias, int r, const float* vc, const float* gsv, float* slab, float* stats,
                    int want_acc, hipStream_t st) {
   if (pc.TW == 8)
@@ -2024,7 +2009,7 @@ void dispatch_pass(const Geom& g, const PassCfg& pc, int n_chunks, const float* 
 }
 
 template <int D>
-void launch_fwd_finish(const Geom& g, const float* slab, const SlabSplit& sp, const float* vc_in, float* s_out,
+void launch_fwd_finish(const DrGeom& g, const float* slab, const SlabSplit& sp, const float* vc_in, float* s_out,
                        float* vc_out, float* v_out, hipStream_t st) {
   const size_t FJD = (size_t)g.F() * g.JD();
   hipLaunchKernelGGL((fwd_finish_kernel<D>), dim3((FJD / 4 + 255) / 256), dim3(256), 0, st, slab, sp, FJD,
@@ -2032,7 +2017,7 @@ void launch_fwd_finish(const Geom& g, const float* slab, const SlabSplit& sp, co
 }
 
 template <int D>
-void launch_bwd_finish(const Geom& g, const float* slab, const SlabSplit& sp, const float* a_init, float* A,
+void launch_bwd_finish(const DrGeom& g, const float* slab, const SlabSplit& sp, const float* a_init, float* A,
                        const float* s, float* gs, hipStream_t st, float* zero = nullptr, size_t n_zero = 0,
                        float* zero1 = nullptr) {
   const size_t FJD = (size_t)g.F() * g.JD();
@@ -2046,17 +2031,17 @@ void launch_bwd_finish(const Geom& g, const float* slab, const SlabSplit& sp, co
 constexpr int gu_tw(int d) { return d >= 64 ? 4 : 2; }
 constexpr int kGuNW = 4;  // waves per gu workgroup
 
-inline int gu_wgroups(const Geom& g) { return (g.NT() + kGuNW * gu_tw(g.dout) - 1) / (kGuNW * gu_tw(g.dout)); }
-inline int padded_frames(const Geom& g) { return (g.F() + 15) / 16 * 16; }
-inline int gu_window(const Geom& g) { return g.lpad + g.rpad + 1; }
-inline size_t gu_lds_bytes(const Geom& g, int nw, int n_per) {
+inline int gu_wgroups(const DrGeom& g) { return (g.NT() + kGuNW * gu_tw(g.dout) - 1) / (kGuNW * gu_tw(g.dout)); }
+inline int padded_frames(const DrGeom& g) { return (g.F() + 15) / 16 * 16; }
+inline int gu_window(const DrGeom& g) { return g.lpad + g.rpad + 1; }
+inline size_t gu_lds_bytes(const DrGeom& g, int nw, int n_per) {
   return (size_t)nw * (15 + gu_window(g)) * gu_row_stride(n_per, g.din) * sizeof(float);
 }
 constexpr size_t kGuLdsMax = 64 * 1024;
 
 // gu i-chunks are ranges of n (all window offsets each): fill ~4 workgroups per CU,
 // then fewest capsules per workgroup, with the gx accumulator inside kGuLdsMax.
-int gu_n_per(const Geom& g, int nw) {
+int gu_n_per(const DrGeom& g, int nw) {
   const int base = (g.F() + 15) / 16 * gu_wgroups(g);
   const int slots = 256 * 4;
   int best = 1;
@@ -2074,20 +2059,12 @@ int gu_n_per(const Geom& g, int nw) {
   return best;
 }
 
-inline size_t gux16_lds_bytes(const Geom& g, int n_per) {
+inline size_t gux16_lds_bytes(const DrGeom& g, int n_per) {
   return (size_t)kGux16NW * (31 + gu_window(g)) * (n_per * 32 + 4) * sizeof(float);
 }
 constexpr size_t kGux16LdsMax = (160 / kGux16Occ - 4) * 1024;   // kGux16Occ workgroups per CU
-// route_gux16_kernel (split-fp16 32x32 tiles) for din = dout = 32 with stored
-// couplings (route_gux_kernel otherwise).  A function of the geometry only: the
-// forward's prep writes the kernel's split W^T planes in place of the fp32 W^T under
-// the same test.
-inline bool use_gux16(const Geom& g) {
-  return g.din == 32 && g.dout == 32 && g.iters >= 2 && g.iters <= 4 &&   // R = 5 spills
-         gux16_lds_bytes(g, 1) <= kGux16LdsMax;
-}
 // n-chunk size: fewest rounds of two workgroups per CU, then fewest capsules each
-int gux16_n_per(const Geom& g, int jgpw) {
+int gux16_n_per(const DrGeom& g, int jgpw) {
   const int base = (g.F() + 31) / 32 * ((g.J + kGux16NW - 1) / kGux16NW / jgpw);
   const int slots = 256 * kGux16Occ;
   int best = 1;
@@ -2105,11 +2082,66 @@ int gux16_n_per(const Geom& g, int jgpw) {
   return best;
 }
 
+// gW-from-scalars plan: capsule chunk, frame splits.
+struct Gw2Plan {
+  int cap, n_rt, n_cc, S, ft_per;
+  size_t pstride;
+};
+// capsules per route_gw3_kernel workgroup (its CAP) for din = d <= 32
+constexpr int gw3_capsules(int d) { return d <= 16 ? 8 : 4; }
+
+// ---------------------------------------------------------------- the layer plan
+// Which kernel family serves each pass of a layer call, and where its buffers lie, is
+// decided once per entry point by resolve() and read from the DrPlan by everything below:
+// the forward writes the operands (fp32 or split-fp16 W^T / x^T) that the backward's gx / gW
+// kernels read because both read the same two enums.
+enum class GxPass {
+  kRecompute,   // route_gu_kernel: logits recomputed, gu blocks left for route_gw_kernel
+  kStored,      // route_gux_kernel: from the stored couplings
+  kStored16,    // route_gux16_kernel: the same on split-fp16 32x32 tiles (W^T as fp16 planes)
+};
+enum class GwPass {
+  kFromGu,   // route_gw_kernel from the gu blocks of GxPass::kRecompute
+  kGw2,      // route_gw2_kernel: from the stored couplings, 4 and 5 iterations
+  kGw3,      // route_gw3_kernel: 2 and 3 iterations
+  kGw16s,    // route_gw16s_kernel: split-fp16 32x32 tiles (x^T as fp16 planes), beside kStored16
+};
+
+// Backward workspace regions (float offsets, each 256-byte aligned).
+struct BwdWs {
+  size_t A, gs, slab, stats, gu_t, xT, WT;
+  size_t gumax;       // max |gu| of the layer (route_gux16_kernel -> route_gw16s_kernel)
+  // only where the 32x32 passes serve the shape:
+  size_t p32;         // scratch (bias sums + partial slabs) of the B1 passes from stored couplings
+  size_t gl;          // gL^r of those passes [iters-1][in_n][JP][Fs], read by the gu / gW passes
+  size_t gwpart;      // partial gW | gbias slabs of the gW pass from stored couplings (S frame splits)
+  size_t bytes;
+};
+
+struct DrPlan {
+  DrGeom g;
+  bool fwd32;             // the 32x32 split-fp16 passes (route_fwd32.hip) serve the shape
+  srf::Fwd32Plan p32;     // their plan, the coupling layout and the gW plan (fwd32 only)
+  srf::Fwd32Cpl cpl;
+  Gw2Plan gw2;
+  bool can_store;         // the shape stores couplings (a function of the geometry alone)
+  bool couplings;         // ... and the caller passed the storage
+  PassCfg pc;             // the exact-fp32 passes (route_pass_kernel): tiles and i-chunks
+  int chunks;
+  int plan_arg;           // the plan in the entry points' encoding (argument 0: the cost model's)
+  GxPass gx;
+  GwPass gw;
+  size_t fwd_bytes;       // forward workspace
+  BwdWs ws;               // backward workspace
+  int JP() const { return p32.JDp / g.dout; }   // capsule stride of the stored couplings
+  const float* hdr(const float* cpl_base) const { return srf::fwd32_hdr(p32, cpl_base + cpl.planes); }
+};
+
 #ifndef SRF_GUX16_JGPW
 #define SRF_GUX16_JGPW 2
 #endif
 template <int R>
-void launch_gux16(const Geom& g, const float* WT, const float* hdr, const float* saved, const float* gs,
+void launch_gux16(const DrGeom& g, const float* WT, const float* hdr, const float* saved, const float* gs,
                   float* g_emb, const float* cst, const float* glst, int JP, float* gumax, hipStream_t st) {
   const int n_all = (g.J + kGux16NW - 1) / kGux16NW;   // output-capsule groups of kGux16NW
   const int jgpw = n_all % SRF_GUX16_JGPW == 0 ? SRF_GUX16_JGPW : 1;
@@ -2123,13 +2155,16 @@ void launch_gux16(const Geom& g, const float* WT, const float* hdr, const float*
                      cst, glst, JP, gumax, jgpw);
 }
 
+// The gx pass.  WT: the W^T operand in the form p.gx asks for; cst / glst / hdr: the stored
+// couplings, their logit gradients and the planes' header (GxPass::kStored*, else null).
 template <int D, int R>
-void launch_gu(const Geom& g, const float* emb, const float* W, const float* WT, const float* bias,
+void launch_gu(const DrPlan& p, const float* emb, const float* W, const float* WT, const float* bias,
                const float* saved, const float* gs, const float* stats, float* gu_t, float* g_emb, hipStream_t st,
-               const float* cst, const float* glst, int JP, const float* hdr = nullptr, float* gumax = nullptr) {
-  if constexpr (R >= 2 && D == 32) {
-    if (cst != nullptr && hdr != nullptr && gumax != nullptr && use_gux16(g)) {
-      launch_gux16<R>(g, WT, hdr, saved, gs, g_emb, cst, glst, JP, gumax, st);
+               const float* cst, const float* glst, const float* hdr, float* gumax) {
+  const DrGeom& g = p.g;
+  if constexpr (D == 32 && R >= 2 && R <= 4) {   // all that resolve() gives GxPass::kStored16
+    if (p.gx == GxPass::kStored16) {
+      launch_gux16<R>(g, WT, hdr, saved, gs, g_emb, cst, glst, p.JP(), gumax, st);
       return;
     }
   }
@@ -2142,73 +2177,116 @@ void launch_gu(const Geom& g, const float* emb, const float* W, const float* WT,
   const int nslots = 15 + gu_window(g);
   const size_t lds = gu_lds_bytes(g, nw, n_per);
   if constexpr (R >= 2 && D <= 32) {   // couplings are stored by the 32x32 forward (din <= 32)
-    if (lds <= kGuLdsMax && cst != nullptr) {
+    if (p.gx == GxPass::kStored) {     // resolve(): the window accumulator fits the LDS
       hipLaunchKernelGGL((route_gux_kernel<D, TW, R>), dim3(n_ftiles * n_wgroups * n_chunks), dim3(64 * nw), lds, st,
                          WT, g.F(), g.T, g.N, g.lpad, g.in_n(), g.J, g.mask_first, n_wgroups, n_chunks, n_per, saved,
-                         gs, g_emb, nslots, cst, glst, JP);
+                         gs, g_emb, nslots, cst, glst, p.JP());
       return;
     }
   }
-  if (lds <= kGuLdsMax)
-    hipLaunchKernelGGL((route_gu_kernel<D, D, TW, R, true>), dim3(n_ftiles * n_wgroups * n_chunks),
-                       dim3(64 * nw), lds, st, emb, W, WT, bias, g.F(), padded_frames(g), g.T, g.N, g.lpad, g.rpad,
-                       g.in_n(), g.J, g.mask_first, n_wgroups, n_chunks, n_per, saved, gs, stats, gu_t, g_emb, nslots,
-                       nullptr, nullptr, 0);
-  else
-    hipLaunchKernelGGL((route_gu_kernel<D, D, TW, R, false>), dim3(n_ftiles * n_wgroups * n_chunks),
-                       dim3(64 * nw), 0, st, emb, W, WT, bias, g.F(), padded_frames(g), g.T, g.N, g.lpad, g.rpad,
-                       g.in_n(), g.J, g.mask_first, n_wgroups, n_chunks, n_per, saved, gs, stats, gu_t, g_emb, nslots,
-                       nullptr, nullptr, 0);
+  const bool ldsacc = lds <= kGuLdsMax;   // else the gx accumulator stays out of LDS
+  hipLaunchKernelGGL((ldsacc ? route_gu_kernel<D, D, TW, R, true> : route_gu_kernel<D, D, TW, R, false>),
+                     dim3(n_ftiles * n_wgroups * n_chunks), dim3(64 * nw), ldsacc ? lds : 0, st, emb, W, WT, bias, g.F(),
+                     padded_frames(g), g.T, g.N, g.lpad, g.rpad, g.in_n(), g.J, g.mask_first, n_wgroups, n_chunks, n_per,
+                     saved, gs, stats, gu_t, g_emb, nslots, nullptr, nullptr, 0);
 }
 
-template <int D>
-void launch_gu_r(const Geom& g, const float* emb, const float* W, const float* WT, const float* bias,
-                 const float* saved, const float* gs, const float* stats, float* gu_t, float* g_emb, hipStream_t st,
-                 const float* cst = nullptr, const float* glst = nullptr, int JP = 0, const float* hdr = nullptr,
-                 float* gumax = nullptr) {
-  switch (g.iters) {
-    case 1: launch_gu<D, 1>(g, emb, W, WT, bias, saved, gs, stats, gu_t, g_emb, st, nullptr, nullptr, 0); break;
-    case 2: launch_gu<D, 2>(g, emb, W, WT, bias, saved, gs, stats, gu_t, g_emb, st, cst, glst, JP, hdr, gumax); break;
-    case 3: launch_gu<D, 3>(g, emb, W, WT, bias, saved, gs, stats, gu_t, g_emb, st, cst, glst, JP, hdr, gumax); break;
-    case 4: launch_gu<D, 4>(g, emb, W, WT, bias, saved, gs, stats, gu_t, g_emb, st, cst, glst, JP, hdr, gumax); break;
-    default: launch_gu<D, 5>(g, emb, W, WT, bias, saved, gs, stats, gu_t, g_emb, st, cst, glst, JP, hdr, gumax); break;
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// fn(Int<R>) for the routing iterations check_geom admits
+template <class Fn>
+auto dispatch_iters(int iters, Fn&& fn) {
+  switch (iters) {
+    case 1: return fn(Int<1>{});
+    case 2: return fn(Int<2>{});
+    case 3: return fn(Int<3>{});
+    case 4: return fn(Int<4>{});
+    default: return fn(Int<5>{});
+  }
+}
+// fn(Int<D>) for the capsule sizes check_geom admits (din == dout)
+template <class Fn>
+int dispatch_din(int din, Fn&& fn) {
+  switch (din) {
+    case 8: return fn(Int<8>{});
+    case 16: return fn(Int<16>{});
+    case 32: return fn(Int<32>{});
+    default: return fn(Int<64>{});
   }
 }
 
+// The gW pass from the stored couplings (GwPass::kGw2, kGw3, kGw16s; din <= 32).
+template <int D>
+int launch_gw2(const DrPlan& pl, const float* xT, const float* saved, const float* gs, const float* cst,
+               const float* glst, float* gwp, float* gbp, hipStream_t st, const float* hdr, const float* gumax) {
+  static_assert(D <= 32, "couplings are stored by the 32x32 forward");
+  const DrGeom& g = pl.g;
+  const Gw2Plan& p = pl.gw2;
+  const int JP = pl.JP(), Fp = padded_frames(g);
+  const int grid = p.n_rt * p.n_cc * p.S;
+  if constexpr (D == 32) {
+    if (pl.gw == GwPass::kGw16s) {   // 2 or 3 iterations
+      const int grid16 = SRF_GW16S_XCD ? (grid + 7) / 8 * 8 : grid;   // the kernel's XCD-aware task order
+      const _Float16* x16 = reinterpret_cast<const _Float16*>(xT);
+      hipLaunchKernelGGL((g.iters == 2 ? route_gw16s_kernel<2, kGw16Cap> : route_gw16s_kernel<3, kGw16Cap>), dim3(grid16),
+                         dim3(256), 0, st, x16, hdr, gumax, saved, gs, cst, glst, g.F(), Fp, g.in_n(), g.J, g.mask_first,
+                         JP, p.n_rt, p.S, p.ft_per, gwp, gbp, p.pstride);
+      SRF_LAUNCH_CHECK("route_gw16s");
+      return SRF_OK;
+    }
+  }
+  if (pl.gw == GwPass::kGw3) {   // 2 or 3 iterations, one capsule chunk size per D
+    constexpr int CAP = gw3_capsules(D);
+    hipLaunchKernelGGL((g.iters == 2 ? route_gw3_kernel<D, 2, CAP> : route_gw3_kernel<D, 3, CAP>), dim3(grid), dim3(256),
+                       0, st, xT, saved, gs, cst, glst, g.F(), Fp, g.in_n(), g.J, g.mask_first, JP, p.n_rt, p.S, p.ft_per,
+                       gwp, gbp, p.pstride);
+    SRF_LAUNCH_CHECK("route_gw3");
+    return SRF_OK;
+  }
+  // GwPass::kGw2: 4 or 5 iterations
+  hipLaunchKernelGGL((g.iters == 4 ? route_gw2_kernel<D, 4> : route_gw2_kernel<D, 5>), dim3(grid), dim3(256), 0, st, xT,
+                     saved, gs, cst, glst, g.F(), Fp, g.in_n(), g.J, g.mask_first, JP, p.n_rt, p.n_cc, p.S, p.ft_per, gwp,
+                     gbp, p.pstride);
+  SRF_LAUNCH_CHECK("route_gw2");
+  return SRF_OK;
+}
 
-// gW-from-scalars plan: capsule chunk, frame splits.  SRF_GW2_SPLITS forces S.
-struct Gw2Plan {
-  int cap, n_rt, n_cc, S, ft_per;
-  size_t pstride;
-};
+// ---------------------------------------------------------------- resolve
+// The predicates below are resolve()'s own: nothing else calls them.
 
-inline int gw2_cap_rt(int d) { return d <= 16 ? 8 : (d == 32 ? 4 : 2); }
+// The 32x32 split-fp16 passes (route_fwd32.hip) serve the shapes they support,
+// route_pass_kernel (exact fp32 16x16x4 tiles) the others (din 64, J*dout > 1024).
+inline bool use_fwd32(const DrGeom& g) { return srf::fwd32_supported(g.din, g.dout, g.J); }
+
+// route_gux16_kernel (split-fp16 32x32 tiles) for din = dout = 32 with stored
+// couplings (route_gux_kernel otherwise).
+inline bool use_gux16(const DrGeom& g) {
+  return g.din == 32 && g.dout == 32 && g.iters >= 2 && g.iters <= 4 &&   // R = 5 spills
+         gux16_lds_bytes(g, 1) <= kGux16LdsMax;
+}
+// route_gw16s_kernel (split-fp16 32x32 tiles, one gu exponent per layer from the gx
+// pass) wherever route_gux16_kernel runs and the routing has at most 3 iterations: the
+// C3 / C4 DR layers.
+inline bool use_gw16s(const DrGeom& g) { return use_gux16(g) && g.iters <= 3; }
 
 // route_gw3_kernel (iters 2..3, din <= 32): 8 capsules per workgroup for din <= 16,
 // 4 for din 32 (two 16-column accumulators per capsule; 8 measured the same at C4);
-// 0: route_gw2_kernel (deeper routing spills at 168 registers, din 64).
-inline int gw3_cap(const Geom& g) {
-  if (g.iters > 3) return 0;
-  return g.din <= 16 ? 8 : g.din == 32 ? 4 : 0;
-}
+// 0: route_gw2_kernel (deeper routing spills at 168 registers).
+inline int gw3_cap(const DrGeom& g) { return g.iters <= 3 && g.din <= 32 ? gw3_capsules(g.din) : 0; }
 
-// route_gw16s_kernel (split-fp16 32x32 tiles, one gu exponent per layer from the gx
-// pass) wherever route_gux16_kernel runs and the routing has at most 3 iterations: the
-// C3 / C4 DR layers.  A function of the geometry only: the forward's prep writes the
-// x^T planes this kernel reads (xt16) under the same test.
-inline bool use_gw16s(const Geom& g) { return use_gux16(g) && g.iters <= 3; }
-
-Gw2Plan gw2_plan(const Geom& g) {
-  const bool g16 = use_gw16s(g);
+// kind: the gW kernel that runs from stored couplings (never GwPass::kFromGu)
+Gw2Plan gw2_plan(const DrGeom& g, GwPass kind) {
+  const bool g16 = kind == GwPass::kGw16s, g3 = kind == GwPass::kGw3;
   Gw2Plan p{};
   const int NT = g.NT();
   const int NCT = g16 ? 2 : (g.din + 15) / 16;
   p.n_rt = g16 ? (g.J + 3) / 4 : (NT + 3) / 4;
-  p.cap = g16 ? kGw16Cap : gw3_cap(g) ? gw3_cap(g) : gw2_cap_rt(g.din);
+  p.cap = g16 ? kGw16Cap : g3 ? gw3_capsules(g.din) : (g.din <= 16 ? 8 : 4);   // kGw2: gw2_cap<D>(), D <= 32
   // workgroups resident at once; route_gw3_kernel (latency-bound) is planned for two
   // resident rounds: at C4 S = 8 frame splits (1280 workgroups) beat S = 4 (640, one
   // round) by 2 %, at C2 the slab term keeps S = 5; route_gw16s_kernel: two per CU
-  const int slots = g16 ? 512 : gw3_cap(g) ? 2 * 768 : 512;
+  const int slots = g16 ? 512 : g3 ? 2 * 768 : 512;
   const double per_tile = g16 ? 120.0 : 200.0;   // cycles per capsule, K step and column tile
   p.n_cc = (g.in_n() + p.cap - 1) / p.cap;
   const int NFT = padded_frames(g) / 16;
@@ -2229,83 +2307,6 @@ Gw2Plan gw2_plan(const Geom& g) {
   }
   return p;
 }
-size_t gw2_part_floats(const Geom& g) { return (size_t)gw2_plan(g).S * gw2_plan(g).pstride; }
-
-template <int D>
-int launch_gw2(const Geom& g, const Gw2Plan& p, const float* xT, const float* saved, const float* gs,
-               const float* cst, const float* glst, int JP, float* gwp, float* gbp, hipStream_t st,
-               const float* hdr = nullptr, const float* gumax = nullptr) {
-  const int grid = p.n_rt * p.n_cc * p.S;
-  if constexpr (D == 32) {
-    if (use_gw16s(g)) {
-      const int grid16 = SRF_GW16S_XCD ? (grid + 7) / 8 * 8 : grid;   // the kernel's XCD-aware task order
-      SRF_REQUIRE(hdr != nullptr && gumax != nullptr, "route_gw16s: needs the forward's header and the gx pass's max");
-      const _Float16* x16 = reinterpret_cast<const _Float16*>(xT);
-#define SRF_GW16S(R_)                                                                                              \
-  hipLaunchKernelGGL((route_gw16s_kernel<R_, kGw16Cap>), dim3(grid16), dim3(256), 0, st, x16, hdr, gumax, saved, gs, \
-                     cst, glst, g.F(), padded_frames(g), g.in_n(), g.J, g.mask_first, JP, p.n_rt, p.S, p.ft_per, gwp, \
-                     gbp, p.pstride)
-      if (g.iters == 2)
-        SRF_GW16S(2);
-      else
-        SRF_GW16S(3);
-#undef SRF_GW16S
-      SRF_LAUNCH_CHECK("route_gw16s");
-      return SRF_OK;
-    }
-  }
-  if constexpr (D <= 32) {
-    if (gw3_cap(g)) {
-#define SRF_GW3(R_, C_)                                                                                           \
-  hipLaunchKernelGGL((route_gw3_kernel<D, R_, C_>), dim3(grid), dim3(256), 0, st, xT, saved, gs, cst, glst, g.F(), \
-                     padded_frames(g), g.in_n(), g.J, g.mask_first, JP, p.n_rt, p.S, p.ft_per, gwp, gbp, p.pstride)
-#define SRF_GW3C(R_) \
-  if (p.cap == 4) SRF_GW3(R_, 4); else SRF_GW3(R_, 8);
-      switch (g.iters) {   // gw3_cap() is 0 past 3 iterations
-        case 2: SRF_GW3C(2) break;
-        default: SRF_GW3C(3) break;
-      }
-#undef SRF_GW3C
-#undef SRF_GW3
-      SRF_LAUNCH_CHECK("route_gw3");
-      return SRF_OK;
-    }
-  }
-#define SRF_GW2(R_)                                                                                              \
-  hipLaunchKernelGGL((route_gw2_kernel<D, R_>), dim3(grid), dim3(256), 0, st, xT, saved, gs, cst, glst, g.F(),    \
-                     padded_frames(g), g.in_n(), g.J, g.mask_first, JP, p.n_rt, p.n_cc, p.S, p.ft_per, gwp, gbp,   \
-                     p.pstride)
-  switch (g.iters) {
-    case 2: SRF_GW2(2); break;
-    case 3: SRF_GW2(3); break;
-    case 4: SRF_GW2(4); break;
-    default: SRF_GW2(5); break;
-  }
-#undef SRF_GW2
-  SRF_LAUNCH_CHECK("route_gw2");
-  return SRF_OK;
-}
-
-// The 32x32 split-fp16 passes (route_fwd32.hip) serve the shapes they support,
-// route_pass_kernel (exact fp32 16x16x4 tiles) the others (din 64, J*dout > 1024).
-inline bool use_fwd32(const Geom& g) { return srf::fwd32_supported(g.din, g.dout, g.J); }
-
-// The plan argument n_chunks of the entry points (route_fwd32.h): 1 .. in_n uniform
-// i-chunks, or srf::kBalFlag | G, the balanced split, which only the 32x32 passes have.
-inline bool plan_balanced(int n_chunks) { return n_chunks > 0 && (n_chunks & srf::kBalFlag) != 0; }
-inline bool plan_arg_ok(const Geom& g, int n_chunks) {
-  return plan_balanced(n_chunks) ? use_fwd32(g) : (n_chunks >= 1 && n_chunks <= g.in_n());
-}
-// i-chunks of the exact-fp32 passes (route_pass_kernel): under a balanced plan they run
-// only a backward without stored couplings, with their own cost model's chunk count
-inline int legacy_chunks(const Geom& g, int n_chunks) {
-  return plan_balanced(n_chunks) ? auto_chunks(g, pass_cfg(g).NW) : n_chunks;
-}
-inline SlabSplit uniform_split(int n) { return SlabSplit{n, 0, 0, 0, 0}; }
-// the slabs of a 32x32 pass r >= 1
-inline SlabSplit pass_split(const Geom& g, const srf::Fwd32Plan& p) {
-  return p.bal_G > 0 ? SlabSplit{p.n_slots, p.bal_G, p.bal_U, g.in_n(), g.JD()} : uniform_split(p.n_chunks);
-}
 
 // Coupling storage is used when the split-bf16 forward runs and the gu pass from
 // stored couplings (route_gux_kernel) fits its window accumulator in LDS; otherwise
@@ -2315,89 +2316,155 @@ inline SlabSplit pass_split(const Geom& g, const srf::Fwd32Plan& p) {
 // iterations, route_gw3_kernel's per-iteration s and gs slices, the forward's
 // c / logZ stores): past 2^31 bytes the forward stores nothing and the backward
 // recomputes the logits instead of reading wrapped offsets.
-inline bool coupling_sizes_fit(const Geom& g) {
-  constexpr size_t kLim = size_t(1) << 31;
-  const srf::Fwd32Plan plan = srf::fwd32_plan(g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J, g.dout);
-  const size_t total = srf::fwd32_cpl_layout(plan, g.F(), g.in_n(), g.din, g.dout, g.J, g.iters).total;
-  return total * 4 < kLim && (size_t)g.F() * g.JD() * 4 * g.iters < kLim;
-}
-
-inline bool couplings_ok(const Geom& g) {
+inline bool couplings_ok(const DrGeom& g, const srf::Fwd32Cpl& cpl) {
   if (!use_fwd32(g) || g.iters < 2 || g.din > 32) return false;
+  constexpr size_t kLim = size_t(1) << 31;
   const int TW = gu_tw(g.dout);
   const int nw = std::min(kGuNW, (g.NT() + TW - 1) / TW);
-  return gu_lds_bytes(g, nw, 1) <= kGuLdsMax && coupling_sizes_fit(g);
+  return gu_lds_bytes(g, nw, 1) <= kGuLdsMax && cpl.total * 4 < kLim && (size_t)g.F() * g.JD() * 4 * g.iters < kLim;
 }
 
+// The plan argument n_chunks of the entry points (route_fwd32.h): 1 .. in_n uniform
+// i-chunks, or srf::kBalFlag | G, the balanced split, which only the 32x32 passes have.
+inline bool plan_balanced(int n_chunks) { return n_chunks > 0 && (n_chunks & srf::kBalFlag) != 0; }
+inline bool plan_arg_ok(const DrPlan& p, int n_chunks) {
+  return plan_balanced(n_chunks) ? p.fwd32 : (n_chunks >= 1 && n_chunks <= p.g.in_n());
+}
+
+// The plan of one call: every kernel choice and buffer offset is taken here, and nowhere
+// else.  It does not judge the arguments (enter() does, for the entry points): the size
+// queries answer for any shape and plan argument, 0 (the cost model's choice) included.
+// have_couplings: the caller passed coupling storage (and, for the backward, wants it read).
+void resolve(DrPlan& p, const DrGeom& g, int n_chunks, bool have_couplings) {
+  p = DrPlan{};
+  p.g = g;
+  p.fwd32 = use_fwd32(g);
+  p.pc = pass_cfg(g);
+  // under a balanced plan the exact-fp32 passes run only a backward without stored
+  // couplings, with their own cost model's chunk count
+  p.chunks = plan_balanced(n_chunks) ? auto_chunks(g, p.pc.NW) : n_chunks;
+  // partial slabs + the i-chunk bias sums of the iteration-0 pass
+  p.fwd_bytes = plan_balanced(n_chunks) ? 0 : (size_t)n_chunks * ((size_t)g.B * g.T + 1) * g.J * g.dout * sizeof(float);
+  GwPass stored_gw = GwPass::kGw2;
+  if (p.fwd32) {
+    p.p32 = srf::fwd32_plan(g, n_chunks);
+    p.fwd_bytes = std::max(p.fwd_bytes, srf::fwd32_workspace(p.p32));
+    p.cpl = srf::fwd32_cpl_layout(p.p32, g);
+    stored_gw = use_gw16s(g) ? GwPass::kGw16s : gw3_cap(g) ? GwPass::kGw3 : GwPass::kGw2;
+    p.gw2 = gw2_plan(g, stored_gw);
+  }
+  p.plan_arg = p.fwd32 ? p.p32.plan_arg : n_chunks == 0 ? auto_chunks(g, p.pc.NW) : p.chunks;
+  p.can_store = couplings_ok(g, p.cpl);
+  p.couplings = have_couplings && p.can_store;
+  p.gx = !p.couplings ? GxPass::kRecompute : use_gux16(g) ? GxPass::kStored16 : GxPass::kStored;
+  p.gw = p.couplings ? stored_gw : GwPass::kFromGu;
+
+  const size_t F = g.F(), JD = g.JD(), in_n = g.in_n(), Fp = padded_frames(g);
+  size_t off = 0;
+  auto take = [&](size_t nfloat) {
+    const size_t o = off;
+    off += srf::align_up(nfloat * sizeof(float), 256);
+    return o / sizeof(float);
+  };
+  BwdWs& w = p.ws;
+  w.A = take(F * JD);
+  w.gs = take((size_t)g.iters * F * JD);
+  w.slab = take((size_t)p.chunks * F * JD);
+  w.stats = take((size_t)(g.iters - 1) * F * in_n * 2);
+  w.gu_t = take(in_n * (size_t)g.NT() * 16 * Fp);
+  w.xT = take(in_n * g.din * Fp);
+  w.WT = take(in_n * JD * g.din);
+  w.gumax = take(64);
+  if (p.fwd32) {
+    w.p32 = take((srf::fwd32_scratch_bytes(p.p32) + 3) / 4);
+    w.gl = take((size_t)std::max(g.iters - 1, 1) * srf::fwd32_frame_stride(g.F()) * in_n * p.JP());
+    w.gwpart = take((size_t)p.gw2.S * p.gw2.pstride);
+  }
+  w.bytes = off;
+}
+
+int check_geom(const DrGeom& g) {
+  SRF_REQUIRE(g.B > 0 && g.T > 0 && g.N > 0 && g.J > 1, "bad shape B=%d T=%d N=%d J=%d", g.B, g.T, g.N, g.J);
+  SRF_REQUIRE(g.lpad >= 0 && g.rpad >= 0, "negative window pad");
+  SRF_REQUIRE(g.iters >= 1 && g.iters <= 5, "routing iterations must be in [1,5], got %d", g.iters);
+  SRF_REQUIRE(g.din == 8 || g.din == 16 || g.din == 32 || g.din == 64, "unsupported in_d %d", g.din);
+  SRF_REQUIRE(g.dout == g.din, "in_d (%d) != out_d (%d) is not supported", g.din, g.dout);
+  SRF_REQUIRE((long long)g.F() * g.in_n() * g.JD() < (1LL << 40), "problem too large");
+  return SRF_OK;
+}
+
+// ---------------------------------------------------------------- the passes
+inline SlabSplit uniform_split(int n) { return SlabSplit{n, 0, 0, 0, 0}; }
+// the slabs of a 32x32 pass r >= 1
+inline SlabSplit pass_split(const DrGeom& g, const srf::Fwd32Plan& p) {
+  return p.bal_G > 0 ? SlabSplit{p.n_slots, p.bal_G, p.bal_U, g.in_n(), g.JD()} : uniform_split(p.n_chunks);
+}
 
 template <int D>
-int fwd_impl(const Geom& g, int n_chunks, const float* emb, const float* W, const float* bias, float* v_out,
-             float* saved, float* couplings, float* slab, hipStream_t st) {
-  const PassCfg pc = pass_cfg(g);
+int fwd_impl(const DrPlan& p, const float* emb, const float* W, const float* bias, float* v_out, float* saved,
+             float* couplings, float* slab, hipStream_t st) {
+  const DrGeom& g = p.g;
+  const srf::Fwd32Plan& plan = p.p32;
+  const srf::Fwd32Cpl& cl = p.cpl;
   const size_t FJD = (size_t)g.F() * g.JD();
   hipEvent_t* ev0 = t_ev_start;
   hipEvent_t* ev1 = t_ev_stop;
   const int nev = t_ev_n;
   t_ev_start = t_ev_stop = nullptr;
   t_ev_n = 0;
-  const bool p32 = use_fwd32(g);
-  srf::Fwd32Plan plan{};
-  srf::Fwd32Cpl cl{};
-  float* bsum = slab + (size_t)n_chunks * FJD;
+  float* bsum = nullptr;
   // split operand planes: in the coupling storage when the backward will reuse them
   void* planes = slab;
   void* scratch = slab;
-  if (p32) {
-    plan = srf::fwd32_plan(g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J, g.dout, n_chunks);
+  if (p.fwd32) {
     float *WT = nullptr, *xT = nullptr;
-    if (couplings != nullptr) {
-      cl = srf::fwd32_cpl_layout(plan, g.F(), g.in_n(), g.din, g.dout, g.J, g.iters);
+    if (p.couplings) {
       planes = couplings + cl.planes;
       WT = couplings + cl.WT;
       xT = couplings + cl.xT;
     } else {
       scratch = static_cast<char*>(static_cast<void*>(slab)) + srf::fwd32_planes_bytes(plan);
     }
-    const int rc = srf::fwd32_prepare(plan, emb, W, bias, g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J, g.dout, planes,
-                                      scratch, WT, xT, st, WT != nullptr && use_gux16(g),
-                                      xT != nullptr && use_gw16s(g));
+    // W^T / x^T in the form the backward's gx / gW kernels will read
+    const int rc = srf::fwd32_prepare(plan, g, emb, W, bias, planes, scratch, WT, xT, st,
+                                      p.gx == GxPass::kStored16, p.gw == GwPass::kGw16s);
     if (rc) return rc;
   } else {
-    const int chunk_len = (g.in_n() + n_chunks - 1) / n_chunks;
-    hipLaunchKernelGGL(bias_chunk_sum_kernel, dim3((n_chunks * g.JD() + 255) / 256), dim3(256), 0, st, bias,
-                       g.in_n(), g.JD(), n_chunks, chunk_len, bsum);
+    bsum = slab + (size_t)p.chunks * FJD;
+    const int chunk_len = (g.in_n() + p.chunks - 1) / p.chunks;
+    hipLaunchKernelGGL(bias_chunk_sum_kernel, dim3((p.chunks * g.JD() + 255) / 256), dim3(256), 0, st, bias,
+                       g.in_n(), g.JD(), p.chunks, chunk_len, bsum);
     SRF_LAUNCH_CHECK("bias_chunk_sum");
   }
   for (int r = 0; r < g.iters; ++r) {
     const float* vc = r > 0 ? saved + (size_t)(2 * (r - 1) + 1) * FJD : nullptr;
     if (r < nev) SRF_HIP_TRY(hipEventRecord(ev0[r], st));
-    if (p32 && r == 0 && srf::fwd32_first_full_supported(plan, g.din, g.dout)) {
+    if (p.fwd32 && r == 0 && srf::fwd32_first_full_supported(plan, g)) {
       // iteration 0 with its finish fused: s^0, Vc^1 (and v for one iteration) directly
-      const int rc = srf::fwd32_first_full(plan, planes, scratch, g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J, g.dout,
-                                           g.mask_first, saved, saved + FJD, g.iters == 1 ? v_out : nullptr, st);
+      const int rc = srf::fwd32_first_full(plan, g, planes, scratch, saved, saved + FJD,
+                                           g.iters == 1 ? v_out : nullptr, st);
       if (rc) return rc;
       if (r < nev) SRF_HIP_TRY(hipEventRecord(ev1[r], st));
       continue;
     }
-    if (p32) {
+    if (p.fwd32) {
       float *cst = nullptr, *lzst = nullptr;
-      if (couplings != nullptr && r > 0) {
+      if (p.couplings && r > 0) {
         const size_t blk = (size_t)srf::fwd32_frame_stride(g.F()) * g.in_n();
-        cst = couplings + cl.c + (size_t)(r - 1) * blk * (plan.JDp / g.dout);
+        cst = couplings + cl.c + (size_t)(r - 1) * blk * p.JP();
         lzst = couplings + cl.lz + (size_t)(r - 1) * blk;
       }
-      const int rc = srf::fwd32_pass(plan, r == 0, planes, scratch, g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J,
-                                     g.dout, g.mask_first, vc, cst, lzst, st);
+      const int rc = srf::fwd32_pass(plan, g, r == 0, planes, scratch, vc, cst, lzst, st);
       if (rc) return rc;
     } else {
-      dispatch_pass<D, MODE_FWD>(g, pc, n_chunks, emb, W, bias, r, vc, r == 0 ? bsum : nullptr, slab, nullptr, 1, st);
+      dispatch_pass<D, MODE_FWD>(g, p.pc, p.chunks, emb, W, bias, r, vc, r == 0 ? bsum : nullptr, slab, nullptr, 1, st);
     }
     SRF_LAUNCH_CHECK("route_pass(fwd)");
     if (r < nev) SRF_HIP_TRY(hipEventRecord(ev1[r], st));
     // the last iteration stores no Vc^R (plane 2R - 1 of saved): nothing reads it
     const bool last = r == g.iters - 1;
-    launch_fwd_finish<D>(g, p32 ? srf::fwd32_slab(plan, scratch) : slab,
-                         !p32 ? uniform_split(n_chunks) : r == 0 ? uniform_split(plan.n_chunks) : pass_split(g, plan),
+    launch_fwd_finish<D>(g, p.fwd32 ? srf::fwd32_slab(plan, scratch) : slab,
+                         !p.fwd32 ? uniform_split(p.chunks) : r == 0 ? uniform_split(plan.n_chunks) : pass_split(g, plan),
                          vc, saved + (size_t)(2 * r) * FJD, last ? nullptr : saved + (size_t)(2 * r + 1) * FJD,
                          last ? v_out : nullptr, st);
     SRF_LAUNCH_CHECK("fwd_finish");
@@ -2405,136 +2472,90 @@ int fwd_impl(const Geom& g, int n_chunks, const float* emb, const float* W, cons
   return SRF_OK;
 }
 
-struct BwdWs {
-  float *A, *gs, *slab, *stats, *gu_t, *xT, *WT;
-  void* p32;          // scratch (bias sums + partial slabs) of the B1 passes from stored couplings
-  float* gl;          // gL^r of those passes [iters-1][in_n][JP][Fs], read by the gu / gW passes
-  float* gwpart;      // partial gW | gbias slabs of route_gw2_kernel (S frame splits)
-  float* gumax;       // max |gu| of the layer (route_gux16_kernel -> route_gw16s_kernel)
-  size_t bytes;
-};
-
-BwdWs bwd_layout(const Geom& g, int n_chunks, void* base) {
-  const size_t F = g.F(), JD = g.JD(), in_n = g.in_n(), Fp = padded_frames(g);
-  size_t off = 0;
-  auto take = [&](size_t nfloat) {
-    size_t o = off;
-    off += srf::align_up(nfloat * sizeof(float), 256);
-    return o;
-  };
-  const size_t oA = take(F * JD), ogs = take((size_t)g.iters * F * JD), oslab = take((size_t)legacy_chunks(g, n_chunks) * F * JD),
-               ostats = take((size_t)(g.iters - 1) * F * in_n * 2), ogu = take(in_n * (size_t)g.NT() * 16 * Fp),
-               oxt = take(in_n * g.din * Fp), owt = take(in_n * JD * g.din);
-  size_t op32 = 0, ogl = 0, ogwp = 0;
-  const size_t ogm = take(64);
-  if (use_fwd32(g)) {
-    const srf::Fwd32Plan plan = srf::fwd32_plan(g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J, g.dout, n_chunks);
-    op32 = take((srf::fwd32_scratch_bytes(plan) + 3) / 4);
-    ogl = take((size_t)std::max(g.iters - 1, 1) * srf::fwd32_frame_stride(g.F()) * in_n * (plan.JDp / g.dout));
-    ogwp = take(gw2_part_floats(g));
-  }
-  char* b = static_cast<char*>(base);
-  BwdWs w;
-  w.A = (float*)(b + oA);
-  w.gs = (float*)(b + ogs);
-  w.slab = (float*)(b + oslab);
-  w.stats = (float*)(b + ostats);
-  w.gu_t = (float*)(b + ogu);
-  w.xT = (float*)(b + oxt);
-  w.WT = (float*)(b + owt);
-  w.p32 = op32 ? (void*)(b + op32) : nullptr;
-  w.gl = ogl ? (float*)(b + ogl) : nullptr;
-  w.gwpart = ogwp ? (float*)(b + ogwp) : nullptr;
-  w.gumax = (float*)(b + ogm);
-  w.bytes = off;
-  return w;
-}
-
 // gW = gu x^T and gbias from the gu blocks the data pass left in the workspace; needs
 // nothing else of the backward, so a caller may run it on a second stream (after the
 // data pass, joined before g_W / g_bias or the workspace are used again).
 template <int D>
-int bwd_weights_impl(const Geom& g, const float* emb, float* g_W, float* g_bias, const BwdWs& w, hipStream_t st,
-                     const float* saved = nullptr, const float* couplings = nullptr) {
+int bwd_weights_impl(const DrPlan& p, const float* emb, float* g_W, float* g_bias, float* ws, hipStream_t st,
+                     const float* saved, const float* couplings) {
+  const DrGeom& g = p.g;
+  const BwdWs& w = p.ws;
   const int Fp = padded_frames(g);
-  if (couplings != nullptr && w.gl != nullptr && g.iters > 1) {
-    // gu formed from the stored couplings / logit gradients (never materialised);
-    // the forward left the windowed x^T in the coupling storage
-    const Gw2Plan p = gw2_plan(g);
-    const srf::Fwd32Plan plan = srf::fwd32_plan(g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J, g.dout);
-    const srf::Fwd32Cpl cl = srf::fwd32_cpl_layout(plan, g.F(), g.in_n(), g.din, g.dout, g.J, g.iters);
-    const bool direct = p.S == 1;
-    float* gwp = direct ? g_W : w.gwpart;
-    float* gbp = direct ? g_bias : w.gwpart + (size_t)g.in_n() * g.JD() * g.din;
-    int rc = launch_gw2<D>(g, p, couplings + cl.xT, saved, w.gs, couplings + cl.c, w.gl, plan.JDp / g.dout, gwp, gbp,
-                           st, srf::fwd32_hdr(plan, couplings + cl.planes), w.gumax);
-    if (rc || direct) return rc;
-    const size_t nw4 = (size_t)g.in_n() * g.JD() * g.din / 4, n4 = p.pstride / 4;
-    hipLaunchKernelGGL(gw_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, st, w.gwpart, p.S, n4, p.pstride, g_W,
-                       nw4, g_bias);
-    SRF_LAUNCH_CHECK("gw_reduce");
-    return SRF_OK;
+  if constexpr (D <= 32) {
+    if (p.gw != GwPass::kFromGu) {
+      // gu formed from the stored couplings / logit gradients (never materialised);
+      // the forward left the windowed x^T in the coupling storage
+      const Gw2Plan& gp = p.gw2;
+      const bool direct = gp.S == 1;
+      float* gwp = direct ? g_W : ws + w.gwpart;
+      float* gbp = direct ? g_bias : ws + w.gwpart + (size_t)g.in_n() * g.JD() * g.din;
+      const int rc = launch_gw2<D>(p, couplings + p.cpl.xT, saved, ws + w.gs, couplings + p.cpl.c, ws + w.gl, gwp, gbp,
+                                   st, p.hdr(couplings), ws + w.gumax);
+      if (rc || direct) return rc;
+      const size_t nw4 = (size_t)g.in_n() * g.JD() * g.din / 4, n4 = gp.pstride / 4;
+      hipLaunchKernelGGL(gw_reduce_kernel, dim3((n4 + 255) / 256), dim3(256), 0, st, ws + w.gwpart, gp.S, n4,
+                         gp.pstride, g_W, nw4, g_bias);
+      SRF_LAUNCH_CHECK("gw_reduce");
+      return SRF_OK;
+    }
   }
   {
     SRF_REQUIRE(g.din <= 64, "window_xt tile holds din <= 64, got %d", g.din);
     const int tiles = (Fp + kXtFrames - 1) / kXtFrames;
     hipLaunchKernelGGL(window_xt_kernel, dim3(g.in_n() * tiles), dim3(256), 0, st, emb, g.F(), Fp, g.T, g.N, g.din,
-                       g.lpad, g.in_n(), w.xT);
+                       g.lpad, g.in_n(), ws + w.xT);
     SRF_LAUNCH_CHECK("window_xt");
   }
   {
     const int tasks = g.in_n() * g.NT();
-    hipLaunchKernelGGL((route_gw_kernel<D>), dim3((tasks + 3) / 4), dim3(256), 0, st, w.gu_t, w.xT, Fp, g.in_n(),
-                       g.JD(), g_W, g_bias);
+    hipLaunchKernelGGL((route_gw_kernel<D>), dim3((tasks + 3) / 4), dim3(256), 0, st, ws + w.gu_t, ws + w.xT, Fp,
+                       g.in_n(), g.JD(), g_W, g_bias);
     SRF_LAUNCH_CHECK("route_gw");
   }
   return SRF_OK;
 }
 
 template <int D>
-int bwd_impl(const Geom& g, int n_chunks, const float* emb, const float* W, const float* bias, const float* saved,
-             const float* couplings, const float* g_v, float* g_emb, float* g_W, float* g_bias, const BwdWs& w,
+int bwd_impl(const DrPlan& p, const float* emb, const float* W, const float* bias, const float* saved,
+             const float* couplings, const float* g_v, float* g_emb, float* g_W, float* g_bias, float* ws,
              hipStream_t st, bool with_weights) {
-  const PassCfg pc = pass_cfg(g);
+  const DrGeom& g = p.g;
+  const BwdWs& w = p.ws;
+  const srf::Fwd32Plan& plan = p.p32;
+  const srf::Fwd32Cpl& cl = p.cpl;
   const size_t FJD = (size_t)g.F() * g.JD();
   const int R = g.iters;
-  const int Fp = padded_frames(g);
   // gs^{R-1} = squash'(s^{R-1}) g_v.  A accumulates sum_{r'>r} gVc^{r'}, the
   // gradient of v^r for r < R-1 (those v reach the loss only through the logits).
   // Iteration 0 needs no backward pass: Vc^0 = 0, so its couplings are uniform
   // and its logits carry no gradient.
-  const bool p32 = couplings != nullptr && w.p32 != nullptr && R > 1;
+  const bool p32 = p.couplings;   // B1 and the gx pass from the forward's stored couplings
+  float* const gsv = ws + w.gs;
   const size_t n_emb = (size_t)g.F() * g.N * g.din;
   // with stored couplings this launch also zeroes g_emb (the gu pass accumulates into it)
-  launch_bwd_finish<D>(g, nullptr, uniform_split(1), g_v, w.A, saved + (size_t)(2 * (R - 1)) * FJD,
-                       w.gs + (size_t)(R - 1) * FJD, st, p32 ? g_emb : nullptr, n_emb, p32 ? w.gumax : nullptr);
+  launch_bwd_finish<D>(g, nullptr, uniform_split(1), g_v, ws + w.A, saved + (size_t)(2 * (R - 1)) * FJD,
+                       gsv + (size_t)(R - 1) * FJD, st, p32 ? g_emb : nullptr, n_emb, p32 ? ws + w.gumax : nullptr);
   SRF_LAUNCH_CHECK("bwd_finish");
-  srf::Fwd32Plan plan{};
-  srf::Fwd32Cpl cl{};
-  if (p32) {
-    // B1 from the forward's stored couplings and operand planes on the split-bf16 32x32 tiles
-    plan = srf::fwd32_plan(g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J, g.dout, n_chunks);
-    cl = srf::fwd32_cpl_layout(plan, g.F(), g.in_n(), g.din, g.dout, g.J, g.iters);
-  }
   for (int r = R - 1; r >= 1; --r) {
     const float* vc = saved + (size_t)(2 * (r - 1) + 1) * FJD;
-    float* stats_r = w.stats + (size_t)(r - 1) * g.F() * g.in_n() * 2;
+    float* stats_r = ws + w.stats + (size_t)(r - 1) * g.F() * g.in_n() * 2;
     if (p32) {
+      // on the split-bf16 32x32 tiles, from the forward's operand planes
       const size_t blk = (size_t)srf::fwd32_frame_stride(g.F()) * g.in_n();
-      const int JP = plan.JDp / g.dout;
-      const int rc = srf::bwd32_pass(plan, couplings + cl.planes, w.p32, g.B, g.T, g.N, g.din, g.lpad, g.rpad, g.J,
-                                     g.dout, couplings + cl.c + (size_t)(r - 1) * blk * JP,
-                                     couplings + cl.lz + (size_t)(r - 1) * blk,
-                                     w.gs + (size_t)r * FJD, stats_r, w.gl + (size_t)(r - 1) * blk * JP, st);
+      const int JP = p.JP();
+      const int rc = srf::bwd32_pass(plan, g, couplings + cl.planes, ws + w.p32,
+                                     couplings + cl.c + (size_t)(r - 1) * blk * JP,
+                                     couplings + cl.lz + (size_t)(r - 1) * blk, gsv + (size_t)r * FJD, stats_r,
+                                     ws + w.gl + (size_t)(r - 1) * blk * JP, st);
       if (rc) return rc;
-      launch_bwd_finish<D>(g, srf::fwd32_slab(plan, w.p32), pass_split(g, plan), nullptr, w.A,
-                             saved + (size_t)(2 * (r - 1)) * FJD, w.gs + (size_t)(r - 1) * FJD, st);
+      launch_bwd_finish<D>(g, srf::fwd32_slab(plan, ws + w.p32), pass_split(g, plan), nullptr, ws + w.A,
+                           saved + (size_t)(2 * (r - 1)) * FJD, gsv + (size_t)(r - 1) * FJD, st);
     } else {
-      const int lc = legacy_chunks(g, n_chunks);
-      dispatch_pass<D, MODE_BWD>(g, pc, lc, emb, W, bias, r, vc, w.gs + (size_t)r * FJD, w.slab, stats_r, 1, st);
+      dispatch_pass<D, MODE_BWD>(g, p.pc, p.chunks, emb, W, bias, r, vc, gsv + (size_t)r * FJD, ws + w.slab, stats_r, 1,
+                                 st);
       SRF_LAUNCH_CHECK("route_pass(bwd)");
-      launch_bwd_finish<D>(g, w.slab, uniform_split(lc), nullptr, w.A, saved + (size_t)(2 * (r - 1)) * FJD,
-                           w.gs + (size_t)(r - 1) * FJD, st);
+      launch_bwd_finish<D>(g, ws + w.slab, uniform_split(p.chunks), nullptr, ws + w.A,
+                           saved + (size_t)(2 * (r - 1)) * FJD, gsv + (size_t)(r - 1) * FJD, st);
     }
     SRF_LAUNCH_CHECK("bwd_finish");
   }
@@ -2542,18 +2563,55 @@ int bwd_impl(const Geom& g, int n_chunks, const float* emb, const float* W, cons
     // W^T for the gu pass; the same launch zeroes g_emb
     const size_t total = (size_t)g.in_n() * g.JD() * g.din + n_emb;
     hipLaunchKernelGGL(transpose_w_kernel, dim3((total + 255) / 256), dim3(256), 0, st, W, g.in_n(), g.JD(), g.din,
-                       w.WT, g_emb, n_emb);
+                       ws + w.WT, g_emb, n_emb);
     SRF_LAUNCH_CHECK("transpose_w");
   }
-  if (p32) {
-    // w.gumax (the gu pass's atomic max) was zeroed by the first bwd_finish launch
-    launch_gu_r<D>(g, emb, W, couplings + cl.WT, bias, saved, w.gs, w.stats, w.gu_t, g_emb, st, couplings + cl.c,
-                   w.gl, plan.JDp / g.dout, srf::fwd32_hdr(plan, couplings + cl.planes), w.gumax);
-  } else
-    launch_gu_r<D>(g, emb, W, w.WT, bias, saved, w.gs, w.stats, w.gu_t, g_emb, st);
+  // stored couplings: w.gumax (the gu pass's atomic max) was zeroed by the first bwd_finish launch
+  dispatch_iters(R, [&](auto r) {
+    launch_gu<D, r>(p, emb, W, p32 ? couplings + cl.WT : ws + w.WT, bias, saved, gsv, ws + w.stats, ws + w.gu_t, g_emb,
+                    st, p32 ? couplings + cl.c : nullptr, p32 ? ws + w.gl : nullptr,
+                    p32 ? p.hdr(couplings) : nullptr, ws + w.gumax);
+  });
   SRF_LAUNCH_CHECK("route_gu");
-  (void)Fp;
-  return with_weights ? bwd_weights_impl<D>(g, emb, g_W, g_bias, w, st, saved, p32 ? couplings : nullptr) : SRF_OK;
+  return with_weights ? bwd_weights_impl<D>(p, emb, g_W, g_bias, ws, st, saved, couplings) : SRF_OK;
+}
+
+// The prologue the entry points share: geometry, pointers, plan, workspace size.
+int enter(DrPlan& p, const DrGeom& g, int n_chunks, bool pointers, bool have_couplings, bool forward,
+          size_t workspace_bytes) {
+  if (const int rc = check_geom(g)) return rc;
+  SRF_REQUIRE(pointers, "null pointer argument");
+  resolve(p, g, n_chunks, have_couplings);
+  SRF_REQUIRE(plan_arg_ok(p, n_chunks), "n_chunks %d: neither in [1, %d] nor a balanced plan of the 32x32 passes",
+              n_chunks, g.in_n());
+  const size_t need = forward ? p.fwd_bytes : p.ws.bytes;
+  if (workspace_bytes < need) {
+    srf::set_error("%s workspace too small: %zu < %zu", forward ? "forward" : "backward", workspace_bytes, need);
+    return SRF_EWORKSPACE;
+  }
+  return SRF_OK;
+}
+
+int route_dr_bwd_entry(const float* emb, const float* W, const float* bias, int B, int T, int N, int din, int lpad,
+                       int rpad, int J, int dout, int iters, int mask_first, int n_chunks, const float* saved,
+                       const float* couplings, const float* g_v, float* g_emb, float* g_W, float* g_bias,
+                       void* workspace, size_t workspace_bytes, void* stream, bool with_weights) {
+  DrPlan p;
+  const int rc = enter(p, DrGeom{B, T, N, din, lpad, rpad, J, dout, iters, mask_first ? 1 : 0}, n_chunks,
+                       emb && W && bias && saved && g_v && g_emb && g_W && g_bias && workspace, couplings != nullptr,
+                       false, workspace_bytes);
+  if (rc) return rc;
+  return dispatch_din(din, [&](auto D) {
+    return bwd_impl<D>(p, emb, W, bias, saved, couplings, g_v, g_emb, g_W, g_bias, static_cast<float*>(workspace),
+                       static_cast<hipStream_t>(stream), with_weights);
+  });
+}
+
+// a size or plan query: any shape, no error return
+DrPlan query(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters, int n_chunks) {
+  DrPlan p;
+  resolve(p, DrGeom{B, T, N, din, lpad, rpad, J, dout, iters, 0}, n_chunks, false);
+  return p;
 }
 
 }  // namespace
@@ -2569,19 +2627,18 @@ int srf_route_dr_set_timing_events(void* const* starts, void* const* stops, int 
 }
 
 int srf_route_dr_auto_chunks(int B, int T, int N, int din, int lpad, int rpad, int J, int dout) {
-  Geom g{B, T, N, din, lpad, rpad, J, dout, 1, 0};
-  if (use_fwd32(g)) return srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout).plan_arg;
-  return auto_chunks(g, pass_cfg(g).NW);
+  return query(B, T, N, din, lpad, rpad, J, dout, 1, 0).plan_arg;
 }
 
 int srf_route_dr_split_table(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks,
                              int* info, int* table, int capacity) {
-  Geom g{B, T, N, din, lpad, rpad, J, dout, 1, 0};
-  SRF_REQUIRE(B > 0 && T > 0 && N > 0 && lpad >= 0 && rpad >= 0 && use_fwd32(g), "split_table: not a 32x32-pass shape");
-  SRF_REQUIRE(n_chunks == 0 || plan_arg_ok(g, n_chunks), "split_table: bad plan argument %d", n_chunks);
+  const bool shape_ok = B > 0 && T > 0 && N > 0 && lpad >= 0 && rpad >= 0;
+  const DrPlan plan = shape_ok ? query(B, T, N, din, lpad, rpad, J, dout, 1, n_chunks) : DrPlan{};
+  SRF_REQUIRE(shape_ok && plan.fwd32, "split_table: not a 32x32-pass shape");
+  SRF_REQUIRE(n_chunks == 0 || plan_arg_ok(plan, n_chunks), "split_table: bad plan argument %d", n_chunks);
   SRF_REQUIRE(info != nullptr && capacity >= 0 && (table != nullptr || capacity == 0), "split_table: null argument");
-  const srf::Fwd32Plan p = srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout, n_chunks);
-  const int in_n = g.in_n();
+  const srf::Fwd32Plan& p = plan.p32;
+  const int in_n = plan.g.in_n();
   const bool bal = p.bal_G > 0;
   const int n_wg = bal ? p.bal_G : p.n_ftiles * p.n_chunks;
   info[0] = bal ? 1 : 0;
@@ -2623,25 +2680,17 @@ size_t srf_route_dr_saved_floats(int B, int T, int J, int dout, int iters) {
 size_t srf_route_dr_fwd_workspace(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters,
                                   int n_chunks) {
   (void)iters;
-  // partial slabs + the i-chunk bias sums of the iteration-0 pass
-  Geom g{B, T, N, din, lpad, rpad, J, dout, 1, 0};
-  size_t need = plan_balanced(n_chunks) ? 0 : (size_t)n_chunks * ((size_t)B * T + 1) * J * dout * sizeof(float);
-  if (use_fwd32(g))
-    need = std::max(need, srf::fwd32_workspace(srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout, n_chunks)));
-  return need;
+  return query(B, T, N, din, lpad, rpad, J, dout, 1, n_chunks).fwd_bytes;
 }
 
 size_t srf_route_dr_bwd_workspace(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters,
                                   int n_chunks) {
-  Geom g{B, T, N, din, lpad, rpad, J, dout, iters, 0};
-  return bwd_layout(g, n_chunks, nullptr).bytes;
+  return query(B, T, N, din, lpad, rpad, J, dout, iters, n_chunks).ws.bytes;
 }
 
 size_t srf_route_dr_coupling_floats(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters) {
-  Geom g{B, T, N, din, lpad, rpad, J, dout, iters, 0};
-  if (!couplings_ok(g)) return 0;
-  return srf::fwd32_cpl_layout(srf::fwd32_plan(B, T, N, din, lpad, rpad, J, dout), B * T, g.in_n(), din, dout, J, iters)
-      .total;
+  const DrPlan p = query(B, T, N, din, lpad, rpad, J, dout, iters, 0);
+  return p.can_store ? p.cpl.total : 0;
 }
 
 int srf_route_dr_fwd(const float* emb, const float* W, const float* bias, int B, int T, int N, int din, int lpad,
@@ -2654,58 +2703,15 @@ int srf_route_dr_fwd(const float* emb, const float* W, const float* bias, int B,
 int srf_route_dr_fwd_ex(const float* emb, const float* W, const float* bias, int B, int T, int N, int din, int lpad,
                         int rpad, int J, int dout, int iters, int mask_first, int n_chunks, float* v_out,
                         float* saved, float* couplings, void* workspace, size_t workspace_bytes, void* stream) {
-  Geom g{B, T, N, din, lpad, rpad, J, dout, iters, mask_first ? 1 : 0};
-  int rc = check_geom(g);
+  DrPlan p;
+  const int rc = enter(p, DrGeom{B, T, N, din, lpad, rpad, J, dout, iters, mask_first ? 1 : 0}, n_chunks,
+                       emb && W && bias && v_out && saved && workspace, couplings != nullptr, true, workspace_bytes);
   if (rc) return rc;
-  SRF_REQUIRE(emb && W && bias && v_out && saved && workspace, "null pointer argument");
-  SRF_REQUIRE(plan_arg_ok(g, n_chunks), "n_chunks %d: neither in [1, %d] nor a balanced plan of the 32x32 passes",
-              n_chunks, g.in_n());
-  const size_t need = srf_route_dr_fwd_workspace(B, T, N, din, lpad, rpad, J, dout, iters, n_chunks);
-  if (workspace_bytes < need) {
-    srf::set_error("forward workspace too small: %zu < %zu", workspace_bytes, need);
-    return SRF_EWORKSPACE;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  float* slab = static_cast<float*>(workspace);
-  if (couplings != nullptr && !couplings_ok(g)) couplings = nullptr;   // nothing to store
-  switch (din) {
-    case 8: return fwd_impl<8>(g, n_chunks, emb, W, bias, v_out, saved, couplings, slab, st);
-    case 16: return fwd_impl<16>(g, n_chunks, emb, W, bias, v_out, saved, couplings, slab, st);
-    case 32: return fwd_impl<32>(g, n_chunks, emb, W, bias, v_out, saved, couplings, slab, st);
-    default: return fwd_impl<64>(g, n_chunks, emb, W, bias, v_out, saved, couplings, slab, st);
-  }
+  return dispatch_din(din, [&](auto D) {
+    return fwd_impl<D>(p, emb, W, bias, v_out, saved, couplings, static_cast<float*>(workspace),
+                       static_cast<hipStream_t>(stream));
+  });
 }
-
-namespace {
-int route_dr_bwd_entry(const float* emb, const float* W, const float* bias, int B, int T, int N, int din, int lpad,
-                       int rpad, int J, int dout, int iters, int mask_first, int n_chunks, const float* saved,
-                       const float* couplings, const float* g_v, float* g_emb, float* g_W, float* g_bias,
-                       void* workspace, size_t workspace_bytes, void* stream, bool with_weights) {
-  Geom g{B, T, N, din, lpad, rpad, J, dout, iters, mask_first ? 1 : 0};
-  int rc = check_geom(g);
-  if (rc) return rc;
-  SRF_REQUIRE(emb && W && bias && saved && g_v && g_emb && g_W && g_bias && workspace, "null pointer argument");
-  SRF_REQUIRE(plan_arg_ok(g, n_chunks), "n_chunks %d: neither in [1, %d] nor a balanced plan of the 32x32 passes",
-              n_chunks, g.in_n());
-  BwdWs w = bwd_layout(g, n_chunks, workspace);
-  if (workspace_bytes < w.bytes) {
-    srf::set_error("backward workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-    return SRF_EWORKSPACE;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (couplings != nullptr && !couplings_ok(g)) couplings = nullptr;
-  switch (din) {
-    case 8:
-      return bwd_impl<8>(g, n_chunks, emb, W, bias, saved, couplings, g_v, g_emb, g_W, g_bias, w, st, with_weights);
-    case 16:
-      return bwd_impl<16>(g, n_chunks, emb, W, bias, saved, couplings, g_v, g_emb, g_W, g_bias, w, st, with_weights);
-    case 32:
-      return bwd_impl<32>(g, n_chunks, emb, W, bias, saved, couplings, g_v, g_emb, g_W, g_bias, w, st, with_weights);
-    default:
-      return bwd_impl<64>(g, n_chunks, emb, W, bias, saved, couplings, g_v, g_emb, g_W, g_bias, w, st, with_weights);
-  }
-}
-}  // namespace
 
 int srf_route_dr_bwd(const float* emb, const float* W, const float* bias, int B, int T, int N, int din, int lpad,
                      int rpad, int J, int dout, int iters, int mask_first, int n_chunks, const float* saved,
@@ -2727,16 +2733,15 @@ int srf_route_dr_bwd_data(const float* emb, const float* W, const float* bias, i
                           int lpad, int rpad, int J, int dout, int iters, int mask_first, int n_chunks,
                           const float* saved, const float* g_v, float* g_emb, void* workspace,
                           size_t workspace_bytes, void* stream) {
-  // g_W / g_bias are not touched by the data pass; the checks want non-null pointers
-  float* unused = reinterpret_cast<float*>(workspace);
-  return route_dr_bwd_entry(emb, W, bias, B, T, N, din, lpad, rpad, J, dout, iters, mask_first, n_chunks, saved,
-                            nullptr, g_v, g_emb, unused, unused, workspace, workspace_bytes, stream, false);
+  return srf_route_dr_bwd_data_ex(emb, W, bias, B, T, N, din, lpad, rpad, J, dout, iters, mask_first, n_chunks, saved,
+                                  nullptr, g_v, g_emb, workspace, workspace_bytes, stream);
 }
 
 int srf_route_dr_bwd_data_ex(const float* emb, const float* W, const float* bias, int B, int T, int N, int din,
                              int lpad, int rpad, int J, int dout, int iters, int mask_first, int n_chunks,
                              const float* saved, const float* couplings, const float* g_v, float* g_emb,
                              void* workspace, size_t workspace_bytes, void* stream) {
+  // g_W / g_bias are not touched by the data pass; the checks want non-null pointers
   float* unused = reinterpret_cast<float*>(workspace);
   return route_dr_bwd_entry(emb, W, bias, B, T, N, din, lpad, rpad, J, dout, iters, mask_first, n_chunks, saved,
                             couplings, g_v, g_emb, unused, unused, workspace, workspace_bytes, stream, false);
@@ -2752,25 +2757,15 @@ int srf_route_dr_bwd_weights(const float* emb, int B, int T, int N, int din, int
 int srf_route_dr_bwd_weights_ex(const float* emb, int B, int T, int N, int din, int lpad, int rpad, int J, int dout,
                                 int iters, int mask_first, int n_chunks, const float* saved, const float* couplings,
                                 float* g_W, float* g_bias, void* workspace, size_t workspace_bytes, void* stream) {
-  Geom g{B, T, N, din, lpad, rpad, J, dout, iters, mask_first ? 1 : 0};
-  int rc = check_geom(g);
+  DrPlan p;
+  const int rc = enter(p, DrGeom{B, T, N, din, lpad, rpad, J, dout, iters, mask_first ? 1 : 0}, n_chunks,
+                       emb && g_W && g_bias && workspace, couplings != nullptr && saved != nullptr, false,
+                       workspace_bytes);
   if (rc) return rc;
-  SRF_REQUIRE(emb && g_W && g_bias && workspace, "null pointer argument");
-  SRF_REQUIRE(plan_arg_ok(g, n_chunks), "n_chunks %d: neither in [1, %d] nor a balanced plan of the 32x32 passes",
-              n_chunks, g.in_n());
-  BwdWs w = bwd_layout(g, n_chunks, workspace);
-  if (workspace_bytes < w.bytes) {
-    srf::set_error("backward workspace too small: %zu < %zu", workspace_bytes, w.bytes);
-    return SRF_EWORKSPACE;
-  }
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (couplings != nullptr && (!couplings_ok(g) || saved == nullptr)) couplings = nullptr;
-  switch (din) {
-    case 8: return bwd_weights_impl<8>(g, emb, g_W, g_bias, w, st, saved, couplings);
-    case 16: return bwd_weights_impl<16>(g, emb, g_W, g_bias, w, st, saved, couplings);
-    case 32: return bwd_weights_impl<32>(g, emb, g_W, g_bias, w, st, saved, couplings);
-    default: return bwd_weights_impl<64>(g, emb, g_W, g_bias, w, st, saved, couplings);
-  }
+  return dispatch_din(din, [&](auto D) {
+    return bwd_weights_impl<D>(p, emb, g_W, g_bias, static_cast<float*>(workspace),
+                               static_cast<hipStream_t>(stream), saved, couplings);
+  });
 }
 
 }  // extern "C"

@@ -1,11 +1,21 @@
-// Host interface of the 32x32-tile split-fp16 DR forward pass (route_fwd32.hip),
-// used by route_dr.hip's srf_route_dr_fwd for the shapes it supports.
+// Host interface of the 32x32-tile split-fp16 DR passes (route_fwd32.hip) and the layer
+// geometry they share with route_dr.hip, whose resolve() decides per shape whether these
+// passes or its own exact-fp32 ones run (DrPlan, there).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
 
 namespace srf {
+
+// One DR layer call.  Every host function of both files takes this, none a list of ints.
+struct DrGeom {
+  int B, T, N, din, lpad, rpad, J, dout, iters, mask_first;
+  int F() const { return B * T; }                     // frames
+  int in_n() const { return N * (lpad + rpad + 1); }   // input capsules of a frame's window
+  int JD() const { return J * dout; }                 // output rows
+  int NT() const { return (J * dout + 15) / 16; }     // 16-row tiles
+};
 
 // Row tiles (of 32 rows) per wave of route_fwd32 / route_bwd32 for din 8, 16.
 constexpr int kFwd32TW = 4;
@@ -36,35 +46,45 @@ __host__ __device__ inline int bal_tile_slots(int ft, int in_n, int U, int G) {
 // workspace queries decode the same plan from the same integer.
 constexpr int kBalFlag = 1 << 20;
 
-struct Fwd32Plan {
+// The plan of the 32x32 passes has two parts.  The shape part is a function of the geometry
+// alone: it lays out the operand planes, and through them the coupling storage that a
+// forward writes and a backward (possibly under another plan argument) reads.  The split
+// part is what the plan argument selects.  fwd32_cpl_layout, fwd32_planes_bytes and
+// fwd32_hdr take a Fwd32Shape, so no layout can depend on a plan argument.
+struct Fwd32Shape {
   int NW;              // waves per workgroup
   int TW;              // 32-row tiles per wave (kFwd32TW; 2 for din 32 with J*dout <= 512)
   int JDp;             // J*dout padded to NW*TW*32 rows
   int xpad;            // zero halves after each x plane (the invalid-frame row)
+  int n_ftiles;        // 32-frame tiles
+  size_t xplane;       // elements per x plane (data + zero row)
+  size_t ws_w, ws_b, ws_x, ws_h;   // operand plane regions (bytes)
+};
+struct Fwd32Split {
   // uniform i-chunks: the iteration-0 pass and its bias sums always, the r >= 1 passes
   // unless the plan is balanced
-  int n_chunks, chunk_len, n_ftiles;
+  int n_chunks, chunk_len;
   int bal_G, bal_U;    // balanced r >= 1 passes: workgroups and units (bal_G = 0: chunked)
   int n_slots;         // slab slots a frame tile of the r >= 1 passes can use
   int plan_arg;        // the plan in the entry points' encoding (what auto_chunks returns)
-  size_t xplane;       // elements per x plane (data + zero row)
-  size_t ws_w, ws_b, ws_x, ws_h, ws_bsum, ws_slab;   // workspace regions (bytes)
+  size_t ws_bsum, ws_slab;   // per-pass scratch regions (bytes)
 };
+struct Fwd32Plan : Fwd32Shape, Fwd32Split {};
 
 bool fwd32_supported(int din, int dout, int J);
 // n_chunks: the plan argument (above)
-Fwd32Plan fwd32_plan(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks = 0);
+Fwd32Plan fwd32_plan(const DrGeom& g, int n_chunks = 0);
 // Operand planes (split W, bias, x and their scale header: written by fwd32_prepare,
 // read by every pass)
 // and per-pass scratch (i-chunk bias sums + partial slabs) may live apart: a
 // training forward keeps its planes for the backward (coupling storage).
-size_t fwd32_planes_bytes(const Fwd32Plan& p);
-size_t fwd32_scratch_bytes(const Fwd32Plan& p);
+size_t fwd32_planes_bytes(const Fwd32Shape& p);
+size_t fwd32_scratch_bytes(const Fwd32Split& p);
 size_t fwd32_workspace(const Fwd32Plan& p);   // planes + scratch
-size_t fwd32_lds(const Fwd32Plan& p);
-float* fwd32_slab(const Fwd32Plan& p, void* scratch);
+size_t fwd32_lds(const Fwd32Shape& p);
+float* fwd32_slab(const Fwd32Split& p, void* scratch);
 // the planes' scale header {2^-(aw+bx), aw, bx} (written by fwd32_prepare)
-const float* fwd32_hdr(const Fwd32Plan& p, const void* planes);
+const float* fwd32_hdr(const Fwd32Shape& p, const void* planes);
 // split W / emb into scaled fp16 planes, bias into bf16 planes, and the i-chunk bias
 // sums (two launches per forward: absmax, prep);
 // WT / xT (nullable): also the fp32 W^T [in_n][din][JD] and window^T [in_n][din][Fp]
@@ -72,32 +92,29 @@ const float* fwd32_hdr(const Fwd32Plan& p, const void* planes);
 // split-fp16 A planes of route_gux16_kernel (same bytes); xt16 (din 32): xT instead
 // holds route_gw16s_kernel's blocked split-fp16 B planes [in_n][Fp/16][2][din][16]
 // (same bytes)
-int fwd32_prepare(const Fwd32Plan& p, const float* emb, const float* W, const float* bias, int B, int T, int N,
-                  int din, int lpad, int rpad, int J, int dout, void* planes, void* scratch, float* WT, float* xT,
-                  hipStream_t st, bool wt16 = false, bool xt16 = false);
+int fwd32_prepare(const Fwd32Plan& p, const DrGeom& g, const float* emb, const float* W, const float* bias,
+                  void* planes, void* scratch, float* WT, float* xT, hipStream_t st, bool wt16 = false,
+                  bool xt16 = false);
 // one routing pass: partial s over i-chunks into fwd32_slab(p, scratch); passes r >= 1
 // also store the couplings c^r (cst) and logZ^r (lzst) when cst != nullptr.
-int fwd32_pass(const Fwd32Plan& p, bool first, const void* planes, void* scratch, int B, int T,
-               int N, int din, int lpad, int rpad, int J, int dout, int mask_first, const float* vc, float* cst,
-               float* lzst, hipStream_t st);
+int fwd32_pass(const Fwd32Plan& p, const DrGeom& g, bool first, const void* planes, void* scratch, const float* vc,
+               float* cst, float* lzst, hipStream_t st);
 // iteration 0 over all input capsules with the finish fused: writes s^0 (s_out),
 // Vc^1 = v^0 (vc_out) and, for one-iteration layers, v (v_out); din = dout = 32
-bool fwd32_first_full_supported(const Fwd32Plan& p, int din, int dout);
-int fwd32_first_full(const Fwd32Plan& p, const void* planes, void* scratch, int B, int T, int N, int din, int lpad,
-                     int rpad, int J, int dout, int mask_first, float* s_out, float* vc_out, float* v_out,
-                     hipStream_t st);
+bool fwd32_first_full_supported(const Fwd32Shape& p, const DrGeom& g);
+int fwd32_first_full(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch, float* s_out,
+                     float* vc_out, float* v_out, hipStream_t st);
 // Coupling storage of one training forward (float offsets): c^r [iters-1][in_n][JP][Fs],
 // logZ^r [iters-1][in_n][Fs], the operand planes, WT, xT; JP = JDp / dout,
-// Fs = fwd32_frame_stride(F).
+// Fs = fwd32_frame_stride(F).  A function of the geometry alone (Fwd32Shape, above).
 struct Fwd32Cpl {
   size_t c, lz, planes, WT, xT, total;
 };
-Fwd32Cpl fwd32_cpl_layout(const Fwd32Plan& p, int F, int in_n, int din, int dout, int J, int iters);
+Fwd32Cpl fwd32_cpl_layout(const Fwd32Shape& p, const DrGeom& g);
 // one backward routing pass r >= 1 from the stored couplings: partial gVc^r over
 // i-chunks into fwd32_slab(p, scratch), the (logZ, sigma) stats and the logit
 // gradients gL^r (glst, laid out as the couplings) of the gu pass
-int bwd32_pass(const Fwd32Plan& p, const void* planes, void* scratch, int B, int T, int N, int din, int lpad,
-               int rpad, int J, int dout, const float* cst, const float* lz, const float* gs, float* stats,
-               float* glst, hipStream_t st);
+int bwd32_pass(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch, const float* cst,
+               const float* lz, const float* gs, float* stats, float* glst, hipStream_t st);
 
 }  // namespace srf

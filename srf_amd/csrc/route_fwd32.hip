@@ -2220,18 +2220,28 @@ static int plan_tw(int din, int JD) {
   return (din == 32 && JD <= 32 * 2 * kMaxNW) ? 2 : kTW;
 }
 
-Fwd32Plan fwd32_plan(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks) {
-  Fwd32Plan p;
-  const int in_n = N * (lpad + rpad + 1);
-  const int JD = J * dout;
-  const int NT = (JD + 31) / 32;
-  p.TW = plan_tw(din, JD);
+// The shape part: tiles and operand planes, from the geometry alone.
+static Fwd32Shape fwd32_shape(const DrGeom& g) {
+  Fwd32Shape p;
+  const int NT = (g.JD() + 31) / 32;
+  p.TW = plan_tw(g.din, g.JD());
   p.NW = 1;
   while (p.NW * p.TW < NT) p.NW *= 2;
   p.JDp = p.NW * p.TW * 32;
-  p.xpad = din == 32 ? 32 : 16;
-  const int F = B * T;
-  const int n_ftiles = (F + 31) / 32;
+  p.xpad = g.din == 32 ? 32 : 16;
+  p.n_ftiles = (g.F() + 31) / 32;
+  p.xplane = (size_t)g.F() * g.N * g.din + p.xpad;
+  p.ws_w = srf::align_up((size_t)2 * g.in_n() * p.JDp * g.din * 2, 256);
+  p.ws_b = srf::align_up((size_t)g.in_n() * p.JDp * 4 * 2, 256);
+  p.ws_x = srf::align_up((size_t)2 * p.xplane * 2, 256);
+  p.ws_h = (size_t)(2 * kAbsBlocks + 64) * 4;   // header + absmax block maxima
+  return p;
+}
+
+Fwd32Plan fwd32_plan(const DrGeom& g, int n_chunks) {
+  Fwd32Plan p;
+  static_cast<Fwd32Shape&>(p) = fwd32_shape(g);
+  const int in_n = g.in_n(), JD = g.JD(), F = g.F(), din = g.din, n_ftiles = p.n_ftiles;
   // How the capsule iterations of a pass are spread over the CUs.  A pass has
   // U = n_ftiles * in_n units of work (one input capsule of one 32-frame tile) and `slots`
   // resident workgroups -- NW > 1: as many per CU as the waves (2 per SIMD) and the LDS (Vc
@@ -2273,7 +2283,6 @@ Fwd32Plan fwd32_plan(int B, int T, int N, int din, int lpad, int rpad, int J, in
   }
   p.n_chunks = best;
   p.chunk_len = (in_n + best - 1) / best;
-  p.n_ftiles = n_ftiles;
   p.bal_G = 0;
   p.bal_U = 0;
   p.n_slots = best;
@@ -2298,41 +2307,35 @@ Fwd32Plan fwd32_plan(int B, int T, int N, int din, int lpad, int rpad, int J, in
       }
     }
   }
-  p.xplane = (size_t)F * N * din + p.xpad;
-  p.ws_w = srf::align_up((size_t)2 * in_n * p.JDp * din * 2, 256);
-  p.ws_b = srf::align_up((size_t)in_n * p.JDp * 4 * 2, 256);
-  p.ws_x = srf::align_up((size_t)2 * p.xplane * 2, 256);
-  p.ws_h = (size_t)(2 * kAbsBlocks + 64) * 4;   // header + absmax block maxima
   p.ws_bsum = srf::align_up((size_t)best * JD * 4, 256);
   // the slabs of the iteration-0 pass (best) or of a later pass (n_slots), whichever are more
   p.ws_slab = srf::align_up((size_t)std::max(best, p.n_slots) * F * JD * 4, 256);
   return p;
 }
 
-const float* fwd32_hdr(const Fwd32Plan& p, const void* planes) {
+const float* fwd32_hdr(const Fwd32Shape& p, const void* planes) {
   return reinterpret_cast<const float*>(static_cast<const char*>(planes) + p.ws_w + p.ws_b + p.ws_x);
 }
-size_t fwd32_planes_bytes(const Fwd32Plan& p) { return p.ws_w + p.ws_b + p.ws_x + p.ws_h; }
-size_t fwd32_scratch_bytes(const Fwd32Plan& p) { return p.ws_bsum + p.ws_slab; }
+size_t fwd32_planes_bytes(const Fwd32Shape& p) { return p.ws_w + p.ws_b + p.ws_x + p.ws_h; }
+size_t fwd32_scratch_bytes(const Fwd32Split& p) { return p.ws_bsum + p.ws_slab; }
 size_t fwd32_workspace(const Fwd32Plan& p) { return fwd32_planes_bytes(p) + fwd32_scratch_bytes(p); }
-float* fwd32_slab(const Fwd32Plan& p, void* scratch) {
+float* fwd32_slab(const Fwd32Split& p, void* scratch) {
   return reinterpret_cast<float*>(static_cast<char*>(scratch) + p.ws_bsum);
 }
 
-size_t fwd32_lds(const Fwd32Plan& p) {
+size_t fwd32_lds(const Fwd32Shape& p) {
   // Vc / gs fragment slabs and softmax statistics (the pipelined din-32 passes add their
   // two shared x buffers, 8 KiB, as a static LDS object)
   return (size_t)p.NW * p.TW * 4 * 64 * 16 + (p.NW > 1 ? (size_t)2 * 32 * p.NW * 8 : 0);
 }
 
-int fwd32_prepare(const Fwd32Plan& p, const float* emb, const float* W, const float* bias, int B, int T, int N,
-                  int din, int lpad, int rpad, int J, int dout, void* planes, void* scratch, float* WT, float* xT,
-                  hipStream_t st, bool wt16, bool xt16) {
+int fwd32_prepare(const Fwd32Plan& p, const DrGeom& g, const float* emb, const float* W, const float* bias,
+                  void* planes, void* scratch, float* WT, float* xT, hipStream_t st, bool wt16, bool xt16) {
   char* base = static_cast<char*>(planes);
   float* hdr = reinterpret_cast<float*>(base + p.ws_w + p.ws_b + p.ws_x);
-  const int in_n = N * (lpad + rpad + 1);
-  hipLaunchKernelGGL(absmax_kernel, dim3(kAbsBlocks, 2), dim3(256), 0, st, W, (size_t)in_n * J * dout * din, emb,
-                     (size_t)B * T * N * din, hdr + 64);
+  const int din = g.din;
+  hipLaunchKernelGGL(absmax_kernel, dim3(kAbsBlocks, 2), dim3(256), 0, st, W, (size_t)g.in_n() * g.JD() * din, emb,
+                     (size_t)g.F() * g.N * din, hdr + 64);
   SRF_LAUNCH_CHECK("absmax");
   PrepArgs P;
   P.W = W;
@@ -2346,17 +2349,17 @@ int fwd32_prepare(const Fwd32Plan& p, const float* emb, const float* W, const fl
   P.bsum = reinterpret_cast<float*>(scratch);
   P.WT = WT;
   P.xT = xT;
-  P.T = T;
-  P.lpad = lpad;
-  P.Fp = (B * T + 15) / 16 * 16;
-  P.in_n = N * (lpad + rpad + 1);
-  P.JD = J * dout;
+  P.T = g.T;
+  P.lpad = g.lpad;
+  P.Fp = (g.F() + 15) / 16 * 16;
+  P.in_n = g.in_n();
+  P.JD = g.JD();
   P.JDp = p.JDp;
   P.din = din;
   P.n_chunks = p.n_chunks;
   P.chunk_len = p.chunk_len;
-  P.F = B * T;
-  P.N = N;
+  P.F = g.F();
+  P.N = g.N;
   P.xplane = p.xplane;
   P.n_a = (size_t)P.in_n * p.JDp * din / 8;
   P.n_b = (size_t)P.in_n * p.JDp;
@@ -2375,54 +2378,67 @@ int fwd32_prepare(const Fwd32Plan& p, const float* emb, const float* W, const fl
   return SRF_OK;
 }
 
-template <int DIN, int DOUT, int NW, int TW = kTW>
-static int launch_rpass(const Fwd32Plan& p, const Args32& a, hipStream_t st) {
-  const size_t lds = fwd32_lds(p);
-  // the pipelined pass holds a second u set: TW = 4 would spill
-  auto kern = (NW > 1 && TW <= 2) ? route_fwd32p_kernel<DIN, DOUT, (NW > 1 ? NW : 2), (TW <= 2 ? TW : 2)>
-                                                    : route_fwd32_kernel<DIN, DOUT, NW, TW>;
-  if (lds > 64 * 1024)
-    SRF_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(p.bal_G > 0 ? p.bal_G : p.n_ftiles * p.n_chunks), dim3(64 * NW), lds, st, a);
-  SRF_LAUNCH_CHECK("route_fwd32");
-  return SRF_OK;
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// The (din, dout) rows that are instantiated: din == dout only, what every entry point
+// requires (route_dr.hip: check_geom).  The kernels keep DIN and DOUT apart, so a
+// din < dout row that fwd32_supported admits comes back by calling fn with its pair here
+// (and lifting that check).
+template <class Fn>
+static int dispatch_row(const DrGeom& g, const char* what, Fn&& fn) {
+  if (g.din == g.dout) {
+    switch (g.din) {
+      case 8: return fn(Int<8>{}, Int<8>{});
+      case 16: return fn(Int<16>{}, Int<16>{});
+      case 32: return fn(Int<32>{}, Int<32>{});
+    }
+  }
+  srf::set_error("%s: unsupported din %d dout %d", what, g.din, g.dout);
+  return SRF_EUNSUPPORTED;
 }
 
-template <int DIN, int DOUT>
-static int launch_pass32_t(const Fwd32Plan& p, bool first, const Args32& a, hipStream_t st) {
-  if (first) {
-    Args32 b = a;
-    b.n_tgroups = p.JDp / (32 * kFTW);
-    const int tasks = (p.n_ftiles + kFFB - 1) / kFFB * b.n_tgroups * p.n_chunks;
-    hipLaunchKernelGGL((route_fwd32_first_kernel<DIN, DOUT>), dim3((tasks + 3) / 4), dim3(256), 0, st, b);
-    SRF_LAUNCH_CHECK("route_fwd32_first");
-    return SRF_OK;
-  }
-  if constexpr (DIN <= 16) {
-    if (p.TW == 2) return p.NW == 1 ? launch_rpass<DIN, DOUT, 1, 2>(p, a, st) : launch_rpass<DIN, DOUT, 2, 2>(p, a, st);
-  }
-  if constexpr (DIN == 32) {
-    if (p.TW == 2) {
+// The (NW, TW) workgroup shapes fwd32_shape can plan for DIN, shared by the forward and
+// the backward r >= 1 passes: fn(Int<NW>, Int<TW>) launches one.
+template <int DIN, class Fn>
+static int dispatch_tiles(const Fwd32Shape& p, Fn&& fn) {
+  if (p.TW == 2) {
+    if constexpr (DIN <= 16) {   // plan_tw: J*dout <= 128, at most two waves
+      return p.NW == 1 ? fn(Int<1>{}, Int<2>{}) : fn(Int<2>{}, Int<2>{});
+    } else {
       switch (p.NW) {
-        case 1: return launch_rpass<DIN, DOUT, 1, 2>(p, a, st);
-        case 2: return launch_rpass<DIN, DOUT, 2, 2>(p, a, st);
-        case 4: return launch_rpass<DIN, DOUT, 4, 2>(p, a, st);
-        default: return launch_rpass<DIN, DOUT, 8, 2>(p, a, st);
+        case 1: return fn(Int<1>{}, Int<2>{});
+        case 2: return fn(Int<2>{}, Int<2>{});
+        case 4: return fn(Int<4>{}, Int<2>{});
+        default: return fn(Int<8>{}, Int<2>{});
       }
     }
   }
   switch (p.NW) {
-    case 1: return launch_rpass<DIN, DOUT, 1>(p, a, st);
-    case 2: return launch_rpass<DIN, DOUT, 2>(p, a, st);
-    case 4: return launch_rpass<DIN, DOUT, 4>(p, a, st);
-    case 8: return launch_rpass<DIN, DOUT, 8>(p, a, st);
-    default: return launch_rpass<DIN, DOUT, kMaxNW>(p, a, st);
+    case 1: return fn(Int<1>{}, Int<kTW>{});
+    case 2: return fn(Int<2>{}, Int<kTW>{});
+    case 4: return fn(Int<4>{}, Int<kTW>{});
+    default: return fn(Int<kMaxNW>{}, Int<kTW>{});
   }
 }
 
-static Args32 make_args32(const Fwd32Plan& p, const void* planes, void* scratch, int B, int T, int N, int din,
-                          int lpad, int rpad, int J, int dout, int mask_first) {
-  const int in_n = N * (lpad + rpad + 1);
+// One r >= 1 pass, forward (args = Args32) or backward (Args32, Bwd32Args), on the plan's grid:
+// the pipelined kernel `piped` for NW > 1 waves of TW <= 2 row tiles (it holds a second u
+// set: TW = 4 would spill), `plain` otherwise.
+template <int NW, int TW, class Kern, class... Args>
+static int launch_rpass(const Fwd32Plan& p, const char* name, Kern piped, Kern plain, hipStream_t st,
+                        const Args&... args) {
+  const size_t lds = fwd32_lds(p);
+  const Kern kern = (NW > 1 && TW <= 2) ? piped : plain;
+  if (lds > 64 * 1024)
+    SRF_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kern, dim3(p.bal_G > 0 ? p.bal_G : p.n_ftiles * p.n_chunks), dim3(64 * NW), lds, st, args...);
+  SRF_LAUNCH_CHECK(name);
+  return SRF_OK;
+}
+
+static Args32 make_args32(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch) {
+  const int in_n = g.in_n();
   const char* base = static_cast<const char*>(planes);
   Args32 a{};
   a.Ws = base;
@@ -2432,53 +2448,54 @@ static Args32 make_args32(const Fwd32Plan& p, const void* planes, void* scratch,
   a.ws_bytes = p.ws_w;
   a.bs_bytes = (size_t)in_n * p.JDp * 8;
   a.xs_bytes = 2 * p.xplane * 2;
-  a.wplane_b = (uint32_t)((size_t)in_n * p.JDp * din * 2);
+  a.wplane_b = (uint32_t)((size_t)in_n * p.JDp * g.din * 2);
   a.xplane_b = (uint32_t)(p.xplane * 2);
   a.zero_off = (uint32_t)((p.xplane - p.xpad) * 2);
-  a.F = B * T;
-  a.T = T;
-  a.N = N;
-  a.lpad = lpad;
+  a.F = g.F();
+  a.T = g.T;
+  a.N = g.N;
+  a.lpad = g.lpad;
   a.in_n = in_n;
-  a.J = J;
+  a.J = g.J;
   a.JDp = p.JDp;
   a.n_chunks = p.n_chunks;
   a.chunk_len = p.chunk_len;
-  a.mask_first = mask_first;
+  a.mask_first = g.mask_first;
   a.n_tgroups = p.NW;
   a.vc = nullptr;
   a.bsum = reinterpret_cast<const float*>(scratch);
   a.slab = fwd32_slab(p, scratch);
   a.cst = nullptr;
   a.lzst = nullptr;
-  a.JP = p.JDp / dout;
-  a.Fs = fwd32_frame_stride(B * T);
+  a.JP = p.JDp / g.dout;
+  a.Fs = fwd32_frame_stride(g.F());
   a.bal_G = p.bal_G;
   a.bal_U = p.bal_U;
   return a;
 }
 
-Fwd32Cpl fwd32_cpl_layout(const Fwd32Plan& p, int F, int in_n, int din, int dout, int J, int iters) {
+Fwd32Cpl fwd32_cpl_layout(const Fwd32Shape& p, const DrGeom& g) {
   Fwd32Cpl c{};
-  const size_t blk = (size_t)fwd32_frame_stride(F) * in_n;
-  const int R1 = std::max(iters - 1, 0);
+  const size_t in_n = g.in_n();
+  const size_t blk = (size_t)fwd32_frame_stride(g.F()) * in_n;
+  const int R1 = std::max(g.iters - 1, 0);
   c.c = 0;
-  c.lz = (size_t)R1 * blk * (p.JDp / dout);
+  c.lz = (size_t)R1 * blk * (p.JDp / g.dout);
   size_t off = c.lz + (size_t)R1 * blk;
   off = (off + 63) / 64 * 64;   // 256-byte aligned regions
   c.planes = off;
   off += (fwd32_planes_bytes(p) + 255) / 256 * 64;
   c.WT = off;
-  off += ((size_t)in_n * din * ((J * dout + 15) / 16 * 16) + 63) / 64 * 64;
+  off += (in_n * g.din * ((g.JD() + 15) / 16 * 16) + 63) / 64 * 64;
   c.xT = off;
-  off += ((size_t)in_n * din * ((F + 15) / 16 * 16) + 63) / 64 * 64;
+  off += (in_n * g.din * ((g.F() + 15) / 16 * 16) + 63) / 64 * 64;
   c.total = off;
   return c;
 }
 
 // Iteration-0 pass with its finish fused (route_fwd32_first_full_kernel): din = dout = 32.
-bool fwd32_first_full_supported(const Fwd32Plan& p, int din, int dout) {
-  return din == 32 && dout == 32 && p.JDp % kFfBM == 0;
+bool fwd32_first_full_supported(const Fwd32Shape& p, const DrGeom& g) {
+  return g.din == 32 && g.dout == 32 && p.JDp % kFfBM == 0;
 }
 
 // Frames per workgroup of the iteration-0 GEMM: the widest tile (fewest operand bytes
@@ -2498,14 +2515,13 @@ static int ff_frames(int n_rt, int F) {
   return 64;
 }
 
-int fwd32_first_full(const Fwd32Plan& p, const void* planes, void* scratch, int B, int T, int N, int din, int lpad,
-                     int rpad, int J, int dout, int mask_first, float* s_out, float* vc_out, float* v_out,
-                     hipStream_t st) {
-  SRF_REQUIRE(fwd32_first_full_supported(p, din, dout), "fwd32_first_full: din %d dout %d JDp %d", din, dout, p.JDp);
+int fwd32_first_full(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch, float* s_out,
+                     float* vc_out, float* v_out, hipStream_t st) {
+  SRF_REQUIRE(fwd32_first_full_supported(p, g), "fwd32_first_full: din %d dout %d JDp %d", g.din, g.dout, p.JDp);
   SRF_REQUIRE(2 * p.xplane * 2 < (1ull << 31) && p.ws_w < (1ull << 31), "fwd32: operand planes exceed 2 GiB");
-  const Args32 a = make_args32(p, planes, scratch, B, T, N, din, lpad, rpad, J, dout, mask_first);
-  const int bn = ff_frames(p.JDp / kFfBM, B * T);
-  const int nb = (p.JDp / kFfBM) * ((B * T + bn - 1) / bn);
+  const Args32 a = make_args32(p, g, planes, scratch);
+  const int bn = ff_frames(p.JDp / kFfBM, g.F());
+  const int nb = (p.JDp / kFfBM) * ((g.F() + bn - 1) / bn);
 #define SRF_FF_LAUNCH(BN)                                                                                          \
   if (bn == BN) {                                                                                                 \
     constexpr int CPS_ = BN >= 96 ? 2 : 1;                                                                        \
@@ -2525,80 +2541,40 @@ int fwd32_first_full(const Fwd32Plan& p, const void* planes, void* scratch, int 
   return SRF_OK;
 }
 
-int fwd32_pass(const Fwd32Plan& p, bool first, const void* planes, void* scratch, int B, int T,
-               int N, int din, int lpad, int rpad, int J, int dout, int mask_first, const float* vc, float* cst,
-               float* lzst, hipStream_t st) {
-  Args32 a = make_args32(p, planes, scratch, B, T, N, din, lpad, rpad, J, dout, mask_first);
+int fwd32_pass(const Fwd32Plan& p, const DrGeom& g, bool first, const void* planes, void* scratch, const float* vc,
+               float* cst, float* lzst, hipStream_t st) {
+  Args32 a = make_args32(p, g, planes, scratch);
   a.vc = vc;
   a.cst = first ? nullptr : cst;
   a.lzst = first ? nullptr : lzst;
   SRF_REQUIRE(2 * p.xplane * 2 < (1ull << 31) && p.ws_w < (1ull << 31), "fwd32: operand planes exceed 2 GiB");
-#define SRF_P32(DI, DO) \
-  if (din == DI && dout == DO) return launch_pass32_t<DI, DO>(p, first, a, st);
-  SRF_P32(8, 8)
-  SRF_P32(8, 16)
-  SRF_P32(8, 32)
-  SRF_P32(16, 16)
-  SRF_P32(16, 32)
-  SRF_P32(32, 32)
-#undef SRF_P32
-  srf::set_error("fwd32: unsupported din %d dout %d", din, dout);
-  return SRF_EUNSUPPORTED;
-}
-
-template <int DIN, int DOUT, int NW, int TW = kTW>
-static int launch_bpass(const Fwd32Plan& p, const Args32& a, const Bwd32Args& b, hipStream_t st) {
-  const size_t lds = fwd32_lds(p);
-  auto kern = (NW > 1 && TW <= 2) ? route_bwd32p_kernel<DIN, DOUT, (NW > 1 ? NW : 2), (TW <= 2 ? TW : 2)>
-                                                    : route_bwd32_kernel<DIN, DOUT, NW, TW>;
-  if (lds > 64 * 1024)
-    SRF_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kern, dim3(p.bal_G > 0 ? p.bal_G : p.n_ftiles * p.n_chunks), dim3(64 * NW), lds, st, a, b);
-  SRF_LAUNCH_CHECK("route_bwd32");
-  return SRF_OK;
-}
-
-template <int DIN, int DOUT>
-static int launch_bpass_t(const Fwd32Plan& p, const Args32& a, const Bwd32Args& b, hipStream_t st) {
-  if constexpr (DIN <= 16) {
-    if (p.TW == 2)
-      return p.NW == 1 ? launch_bpass<DIN, DOUT, 1, 2>(p, a, b, st) : launch_bpass<DIN, DOUT, 2, 2>(p, a, b, st);
-  }
-  if constexpr (DIN == 32) {
-    if (p.TW == 2) {
-      switch (p.NW) {
-        case 1: return launch_bpass<DIN, DOUT, 1, 2>(p, a, b, st);
-        case 2: return launch_bpass<DIN, DOUT, 2, 2>(p, a, b, st);
-        case 4: return launch_bpass<DIN, DOUT, 4, 2>(p, a, b, st);
-        default: return launch_bpass<DIN, DOUT, 8, 2>(p, a, b, st);
-      }
+  return dispatch_row(g, "fwd32", [&](auto di, auto dout) {
+    if (first) {
+      Args32 b = a;
+      b.n_tgroups = p.JDp / (32 * kFTW);
+      const int tasks = (p.n_ftiles + kFFB - 1) / kFFB * b.n_tgroups * p.n_chunks;
+      hipLaunchKernelGGL((route_fwd32_first_kernel<di, dout>), dim3((tasks + 3) / 4), dim3(256), 0, st, b);
+      SRF_LAUNCH_CHECK("route_fwd32_first");
+      return SRF_OK;
     }
-  }
-  switch (p.NW) {
-    case 1: return launch_bpass<DIN, DOUT, 1>(p, a, b, st);
-    case 2: return launch_bpass<DIN, DOUT, 2>(p, a, b, st);
-    case 4: return launch_bpass<DIN, DOUT, 4>(p, a, b, st);
-    case 8: return launch_bpass<DIN, DOUT, 8>(p, a, b, st);
-    default: return launch_bpass<DIN, DOUT, kMaxNW>(p, a, b, st);
-  }
+    return dispatch_tiles<di>(p, [&](auto nw, auto tw) {
+      return launch_rpass<nw, tw>(p, "route_fwd32", route_fwd32p_kernel<di, dout, (nw > 1 ? nw : 2), (tw <= 2 ? tw : 2)>,
+                                  route_fwd32_kernel<di, dout, nw, tw>, st, a);
+    });
+  });
 }
 
-int bwd32_pass(const Fwd32Plan& p, const void* planes, void* scratch, int B, int T, int N, int din, int lpad,
-               int rpad, int J, int dout, const float* cst, const float* lz, const float* gs, float* stats,
-               float* glst, hipStream_t st) {
-  Args32 a = make_args32(p, planes, scratch, B, T, N, din, lpad, rpad, J, dout, 0);
-  Bwd32Args b{cst, lz, gs, stats, glst};
-#define SRF_B32(DI, DO) \
-  if (din == DI && dout == DO) return launch_bpass_t<DI, DO>(p, a, b, st);
-  SRF_B32(8, 8)
-  SRF_B32(8, 16)
-  SRF_B32(8, 32)
-  SRF_B32(16, 16)
-  SRF_B32(16, 32)
-  SRF_B32(32, 32)
-#undef SRF_B32
-  srf::set_error("bwd32: unsupported din %d dout %d", din, dout);
-  return SRF_EUNSUPPORTED;
+int bwd32_pass(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch, const float* cst,
+               const float* lz, const float* gs, float* stats, float* glst, hipStream_t st) {
+  Args32 a = make_args32(p, g, planes, scratch);
+  a.mask_first = 0;   // the mask is in the stored couplings; the backward kernels do not read it
+  const Bwd32Args b{cst, lz, gs, stats, glst};
+  return dispatch_row(g, "bwd32", [&](auto di, auto dout) {
+    return dispatch_tiles<di>(p, [&](auto nw, auto tw) {
+      return launch_rpass<nw, tw>(p, "route_bwd32", route_bwd32p_kernel<di, dout, (nw > 1 ? nw : 2), (tw <= 2 ? tw : 2)>,
+                                  route_bwd32_kernel<di, dout, nw, tw>, st, a, b);
+    });
+  });
 }
 
 }  // namespace srf
