@@ -412,6 +412,24 @@ size_t srf_ctc_workspace(int B, int Tmax, int C, int Lmax);
 int srf_ctc_loss(const float* logits, const int* labels, const int* label_len, const int* logit_len, int B, int Tmax,
                  int C, int Lmax, int blank, float grad_scale, float* nll, float* grad, void* workspace,
                  size_t workspace_bytes, void* stream);
+/* srf_ctc_align: CTC forced alignment (Viterbi) of the given labels, same calling
+ * convention as srf_ctc_loss (T_b = min(logit_len[b], Tmax)).  With lp = log_softmax in
+ * fp32 and the extended label of S = 2 L_b + 1 states (even: blank, 2k + 1: label k), the
+ * result is the path that starts in state 0 or 1, ends in S - 1 or S - 2, moves by 0 or
+ * +1 per frame, by +2 only into a label state whose label differs from the label two
+ * states back, and maximises the sum of lp[t, ext[state_t]]; score [B] is that sum.
+ * Ties: among equal predecessors the lowest source state wins (+2 before +1 before
+ * stay); at the last frame S - 2 unless S - 1 is strictly larger.
+ * states [B][Tmax]: the state per frame, -1 for t >= T_b.  tok_start / tok_end [B][Lmax]:
+ * first frame of label k's run and one past its last, -1 for k >= L_b.  tok_logp
+ * [B][Lmax]: sum of lp over label k's frames, 0 where there is no label.  T_b = 0 with
+ * L_b = 0 scores 0; L_b = 0 keeps every frame in state 0; an infeasible utterance (T_b
+ * too short for its labels) scores -inf and all its other outputs are -1 / 0.  The token
+ * outputs and labels may be NULL when Lmax = 0.  workspace: 16-byte aligned. */
+size_t srf_ctc_align_workspace(int B, int Tmax, int C, int Lmax);
+int srf_ctc_align(const float* logits, const int* labels, const int* label_len, const int* logit_len, int B, int Tmax,
+                  int C, int Lmax, int blank, int* states, int* tok_start, int* tok_end, float* tok_logp, float* score,
+                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Chunked streaming inference (srf_amd/streaming.py) --------------------
  * srf_ctc_greedy_n: best-path decoding (per-frame arg-max, repeats merged, blanks
@@ -423,6 +441,12 @@ int srf_ctc_loss(const float* logits, const int* labels, const int* label_len, c
  * lowest class index wins (torch.argmax).  One wave per stream; any C >= 2, n >= 0. */
 int srf_ctc_greedy_n(const float* logits, const int* n_valid, int B, int n, int C, int blank, int* prev, int* labels,
                      int* count, void* stream);
+/* srf_ctc_greedy_frames_n: srf_ctc_greedy_n with one more output, frames [B][n]:
+ * frames[b][i] = frame0 + f for the chunk frame f at which labels[b][i] was emitted, the
+ * first frame of its arg-max run (a run that continues across a chunk edge was emitted in
+ * the earlier chunk).  labels, count and prev are those of srf_ctc_greedy_n. */
+int srf_ctc_greedy_frames_n(const float* logits, const int* n_valid, int B, int n, int C, int blank, int frame0,
+                            int* prev, int* labels, int* frames, int* count, void* stream);
 /* srf_ctc_beam_*: CTC prefix beam search on the device (tf.nn.ctc_beam_search_decoder
  * with top_paths = 1 as process_test_step calls it; the algorithm of srf_ctc_beam_search
  * in srf_data.h, which defines the result), batched and resumable: one workgroup per

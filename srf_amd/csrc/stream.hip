@@ -4,7 +4,8 @@
 // srf_ctc_greedy_n: incremental best-path decoding (arg-max per frame, merge repeats,
 // drop blanks; ctc.greedy_decode on the host) of the frames a chunk added, carrying the
 // last frame's arg-max across chunk edges, so that a chunk's hypothesis needs no copy of
-// its logits to the host.
+// its logits to the host.  srf_ctc_greedy_frames_n is the same launch with one more
+// output: the frame at which each label was emitted.
 //
 // srf_stream_advance_n: the sliding state buffers of every stage move their kept tail
 // to the front, all buffers of all streams in one launch.
@@ -19,12 +20,14 @@ namespace {
 // lane 0 runs the collapse.
 __global__ __launch_bounds__(64) void ctc_greedy_kernel(const float* __restrict__ logits,
                                                         const int* __restrict__ n_valid, int n, int C, int blank,
-                                                        int* __restrict__ prev, int* __restrict__ labels,
+                                                        int frame0, int* __restrict__ prev,
+                                                        int* __restrict__ labels, int* __restrict__ frames,
                                                         int* __restrict__ count) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int nv = max(0, min(n_valid[b], n));
   const float* x = logits + (size_t)b * n * C;
   int* out = labels + (size_t)b * n;
+  int* fout = frames ? frames + (size_t)b * n : nullptr;   // srf_ctc_greedy_frames_n only
   int last = prev[b], cnt = 0;
   for (int f = 0; f < nv; ++f) {
     const float* row = x + (size_t)f * C;
@@ -46,7 +49,10 @@ __global__ __launch_bounds__(64) void ctc_greedy_kernel(const float* __restrict_
         arg = oa;
       }
     }
-    if (lane == 0 && arg != last && arg != blank) out[cnt++] = arg;
+    if (lane == 0 && arg != last && arg != blank) {
+      if (fout) fout[cnt] = frame0 + f;   // the first frame of the label's arg-max run
+      out[cnt++] = arg;
+    }
     last = arg;
   }
   if (lane == 0) {
@@ -123,8 +129,20 @@ extern "C" int srf_ctc_greedy_n(const float* logits, const int* n_valid, int B, 
   SRF_REQUIRE(n_valid && prev && count, "ctc_greedy: null pointer argument");
   SRF_REQUIRE(n == 0 || (logits && labels), "ctc_greedy: null logits / labels with n = %d", n);
   hipLaunchKernelGGL(ctc_greedy_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream), logits,
-                     n_valid, n, C, blank, prev, labels, count);
+                     n_valid, n, C, blank, 0, prev, labels, static_cast<int*>(nullptr), count);
   SRF_LAUNCH_CHECK("ctc_greedy");
+  return SRF_OK;
+}
+
+extern "C" int srf_ctc_greedy_frames_n(const float* logits, const int* n_valid, int B, int n, int C, int blank,
+                                       int frame0, int* prev, int* labels, int* frames, int* count, void* stream) {
+  SRF_REQUIRE(B >= 1 && n >= 0 && C >= 2, "ctc_greedy_frames: need B >= 1, n >= 0, C >= 2 (B=%d n=%d C=%d)", B, n, C);
+  SRF_REQUIRE(n_valid && prev && count, "ctc_greedy_frames: null pointer argument");
+  SRF_REQUIRE(n == 0 || (logits && labels && frames), "ctc_greedy_frames: null logits / labels / frames with n = %d",
+              n);
+  hipLaunchKernelGGL(ctc_greedy_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream), logits,
+                     n_valid, n, C, blank, frame0, prev, labels, frames, count);
+  SRF_LAUNCH_CHECK("ctc_greedy_frames");
   return SRF_OK;
 }
 

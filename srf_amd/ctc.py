@@ -53,6 +53,92 @@ def greedy_decode_device(logits, n_valid, blank_index, prev):
     return ops.ctc_greedy_chunk(logits.contiguous(), n_valid, blank_index, prev)
 
 
+def greedy_decode_frames_device(logits, n_valid, blank_index, prev, frame0=0):
+    """greedy_decode_device with the time of every label (srf_ctc_greedy_frames_n):
+    returns (labels [B, n], frames [B, n], count [B]) int32 on the device, frames[b, i] =
+    frame0 + the chunk frame at which labels[b, i] was emitted, i.e. the first frame of
+    its arg-max run; a run that continues across a chunk edge belongs to the earlier
+    chunk.  labels, count and prev are those of greedy_decode_device."""
+    n_valid = n_valid.to(device=logits.device, dtype=torch.int32).contiguous()
+    return ops.ctc_greedy_frames_chunk(logits.contiguous(), n_valid, blank_index, prev, frame0)
+
+
+class Alignment:
+    """Result of ``forced_align``, on the device: ``states`` [B, T] int32 (the extended-
+    label state per frame: even = blank, 2k + 1 = label k; -1 past the utterance's end and
+    for an infeasible utterance), ``token_start`` / ``token_end`` [B, Lmax] int32 (first
+    frame of label k's run and one past its last; -1 where there is no label),
+    ``token_logp`` [B, Lmax] (sum of the log-probabilities over the run) and ``score`` [B]
+    (the path's log-probability, -inf for an infeasible utterance).  ``classes`` is the
+    class per frame (-1 where ``states`` is -1); ``spans()`` the host view."""
+
+    def __init__(self, labels, label_lengths, blank_index, states, token_start, token_end, token_logp, score):
+        self.labels, self.label_lengths, self.blank_index = labels, label_lengths, int(blank_index)
+        self.states, self.token_start, self.token_end = states, token_start, token_end
+        self.token_logp, self.score = token_logp, score
+        self._classes = self._spans = None
+
+    @property
+    def classes(self):
+        if self._classes is None:
+            st = self.states.to(torch.int64)
+            cls = torch.full_like(st, self.blank_index)
+            if self.labels.shape[1] > 0:
+                lab = torch.gather(self.labels.to(torch.int64), 1, (st.clamp(min=1) - 1) // 2)
+                cls = torch.where(st % 2 == 1, lab, cls)
+            self._classes = torch.where(st < 0, st, cls).to(torch.int32)
+        return self._classes
+
+    def spans(self):
+        """Per utterance a list of (label, start, end): label k sits at frames [start,
+        end).  Empty for an infeasible utterance.  One copy to the host, kept."""
+        if self._spans is None:
+            Lmax = self.labels.shape[1]
+            packed = torch.cat([self.labels.to(torch.int32), self.token_start, self.token_end,
+                                self.label_lengths.to(torch.int32)[:, None]], dim=1).cpu().tolist()
+            self._spans = []
+            for row in packed:
+                n = min(max(row[-1], 0), Lmax)
+                lab, st, en = row[:Lmax], row[Lmax:2 * Lmax], row[2 * Lmax:3 * Lmax]
+                self._spans.append([(lab[k], st[k], en[k]) for k in range(n) if st[k] >= 0])
+        return [list(s) for s in self._spans]
+
+
+def forced_align(logits, logit_lengths, labels, label_lengths=None, blank_index=0):
+    """CTC forced alignment on the device (srf_ctc_align): the most probable frame-level
+    path of each utterance's labels through logits [B, T, C].  ``labels``: a tensor
+    [B, Lmax] with ``label_lengths`` [B], or a list of B label lists.  Returns an
+    ``Alignment``; the logits are not copied to the host."""
+    if not torch.is_tensor(logits) or logits.dim() != 3 or not logits.is_cuda:
+        shape, where = tuple(getattr(logits, 'shape', ())), getattr(logits, 'device', 'the host')
+        raise ValueError(f'logits must be a device tensor [B, T, C], got {shape} on {where}')
+    B, T, C = logits.shape
+    if B < 1 or T < 1 or C < 2:
+        raise ValueError(f'logits [B, T, C] need B >= 1, T >= 1 and C >= 2, got {tuple(logits.shape)}')
+    if not 0 <= int(blank_index) < C:
+        raise ValueError(f'blank index {blank_index} outside [0, {C})')
+    dev = logits.device
+    if torch.is_tensor(labels):
+        if labels.dim() != 2 or labels.shape[0] != B or label_lengths is None:
+            raise ValueError(f'a label tensor must be [{B}, Lmax] and come with label_lengths')
+        lab = labels.to(device=dev, dtype=torch.int32).contiguous()
+        lab_len = torch.as_tensor(label_lengths).to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        if len(labels) != B or label_lengths is not None:
+            raise ValueError(f'a label list must hold {B} label lists and come without label_lengths')
+        Lmax = max([len(l) for l in labels] + [0])
+        rows = [list(l) + [0] * (Lmax - len(l)) for l in labels]
+        lab = torch.tensor(rows, dtype=torch.int32).reshape(B, Lmax).to(dev)
+        lab_len = torch.tensor([len(l) for l in labels], dtype=torch.int32, device=dev)
+    if tuple(lab_len.shape) != (B,):
+        raise ValueError(f'label_lengths must have shape ({B},), got {tuple(lab_len.shape)}')
+    lens = torch.as_tensor(logit_lengths).to(device=dev, dtype=torch.int32).contiguous()
+    if tuple(lens.shape) != (B,):
+        raise ValueError(f'logit_lengths must have shape ({B},), got {tuple(lens.shape)}')
+    out = ops.ctc_align(logits.detach().float().contiguous(), lab, lab_len, lens, int(blank_index))
+    return Alignment(lab, lab_len, blank_index, *out)
+
+
 BEAM_MAX_WIDTH = 128     # SRF_CTC_BEAM_MAX_WIDTH
 BEAM_MAX_CLASSES = 128   # SRF_CTC_BEAM_MAX_CLASSES
 

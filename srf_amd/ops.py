@@ -553,6 +553,47 @@ def ctc_loss(logits, labels, label_len, logit_len, blank):
     return CtcLoss.apply(logits, _i32(labels), _i32(label_len), _i32(logit_len), blank)
 
 
+def ctc_align(logits, labels, label_len, logit_len, blank):
+    """srf_ctc_align: the best path of the given labels through logits [B, T, C]
+    (Viterbi).  Returns device tensors (states [B, T] int32, tok_start, tok_end [B, Lmax]
+    int32, tok_logp [B, Lmax] float32, score [B] float32)."""
+    B, T, C = logits.shape
+    _check_dev('logits', logits, (B, T, C))
+    labels, label_len, logit_len = _i32(labels), _i32(label_len), _i32(logit_len)
+    Lmax = labels.shape[1]
+    L = _lib.lib()
+    dev = logits.device
+    states = torch.empty((B, T), device=dev, dtype=torch.int32)
+    tok_start = torch.empty((B, Lmax), device=dev, dtype=torch.int32)
+    tok_end = torch.empty((B, Lmax), device=dev, dtype=torch.int32)
+    tok_logp = torch.empty((B, Lmax), device=dev, dtype=torch.float32)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    wb = L.srf_ctc_align_workspace(B, T, C, Lmax)
+    ws = torch.empty(max(wb, 16), device=dev, dtype=torch.uint8)
+    _lib.check(L.srf_ctc_align(_ptr(logits.detach()), _ptr(labels), _ptr(label_len), _ptr(logit_len), B, T, C, Lmax,
+                               int(blank), _ptr(states), _ptr(tok_start), _ptr(tok_end), _ptr(tok_logp), _ptr(score),
+                               _ptr(ws), wb, _stream()), 'srf_ctc_align')
+    return states, tok_start, tok_end, tok_logp, score
+
+
+def ctc_greedy_frames_chunk(logits, n_valid, blank, prev, frame0):
+    """srf_ctc_greedy_frames_n: ctc_greedy_chunk with the frame at which each label was
+    emitted, counted from frame0 at the chunk's first frame.  Returns (labels [B, n]
+    int32, frames [B, n] int32, count [B] int32), all on the device."""
+    B, n, C = logits.shape
+    _check_dev('logits', logits, (B, n, C))
+    for name, t in (('n_valid', n_valid), ('prev', prev)):
+        if not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous int32 device tensor of shape ({B},)')
+    labels = torch.empty((B, n), device=logits.device, dtype=torch.int32)
+    frames = torch.empty((B, n), device=logits.device, dtype=torch.int32)
+    count = torch.empty(B, device=logits.device, dtype=torch.int32)
+    _lib.check(_lib.lib().srf_ctc_greedy_frames_n(_ptr(logits), _ptr(n_valid), B, n, C, int(blank), int(frame0),
+                                                  _ptr(prev), _ptr(labels), _ptr(frames), _ptr(count), _stream()),
+               'srf_ctc_greedy_frames_n')
+    return labels, frames, count
+
+
 def ctc_greedy_chunk(logits, n_valid, blank, prev):
     """srf_ctc_greedy_n: best-path labels of one chunk of logits [B, n, C] (the first
     n_valid[b] frames of stream b), continuing from prev [B] int32 (the last frame's

@@ -87,16 +87,24 @@ def check_ended(lengths, ended, pushed, n):
 class StreamOut:
     """What one ``push`` / ``finish`` emitted: output frames [t0, t0 + m) of every
     stream.  ``logits`` [B, m, C] (device); ``labels``: per stream, the greedy labels
-    these frames added (fetched from the device on first use)."""
+    these frames added; ``label_frames``: per stream, the global output frame at which
+    each of those labels was emitted, the first frame of its arg-max run (both fetched
+    from the device together, on first use)."""
 
     def __init__(self, router, t0, logits):
-        self._router, self.t0, self.logits, self._labels = router, t0, logits, None
+        self._router, self.t0, self.logits, self._labels, self._frames = router, t0, logits, None, None
 
     @property
     def labels(self):
         if self._labels is None:
             self._router._fetch_labels()
         return self._labels
+
+    @property
+    def label_frames(self):
+        if self._frames is None:
+            self._router._fetch_labels()
+        return self._frames
 
 
 class StreamingRouter:
@@ -173,7 +181,8 @@ class StreamingRouter:
         self._lengths = [None] * self.B
         self._finished = False
         self._hyp = [[] for _ in range(self.B)]
-        self._pending = []      # (StreamOut, labels, count) not yet fetched from the device
+        self._hyp_frames = [[] for _ in range(self.B)]
+        self._pending = []      # (StreamOut, labels, frames, count) not yet fetched from the device
         if self._beam is not None:
             self._beam.reset()
         self._beam_best = None  # (labels, scores) of the frames pushed so far, once fetched
@@ -203,12 +212,21 @@ class StreamingRouter:
         self._fetch_labels()
         return [list(h) for h in self._hyp]
 
+    @property
+    def hypothesis_frames(self):
+        """Per stream, the global output frame at which each label of ``hypotheses`` was
+        emitted (an output frame is 4 input frames)."""
+        self._fetch_labels()
+        return [list(f) for f in self._hyp_frames]
+
     def _fetch_labels(self):
-        for out, labels, count in self._pending:
-            labels, count = labels.cpu().tolist(), count.cpu().tolist()
+        for out, labels, frames, count in self._pending:
+            labels, frames, count = labels.cpu().tolist(), frames.cpu().tolist(), count.cpu().tolist()
             out._labels = [labels[b][:count[b]] for b in range(self.B)]
+            out._frames = [frames[b][:count[b]] for b in range(self.B)]
             for b in range(self.B):
                 self._hyp[b].extend(out._labels[b])
+                self._hyp_frames[b].extend(out._frames[b])
         self._pending = []
 
     # ------------------------------------------------------------------ stages
@@ -273,8 +291,8 @@ class StreamingRouter:
     def _advance(self, shift, keep):
         ops.stream_advance([(t, self.cap, shift, keep) for t in self._emb + self._v])
 
-    def _greedy(self, logits, n_valid):
-        return ctc.greedy_decode_device(logits, n_valid, self.blank, self._prev)
+    def _greedy(self, logits, n_valid, t0):
+        return ctc.greedy_decode_frames_device(logits, n_valid, self.blank, self._prev, t0)
 
     # ------------------------------------------------------------------ the chunk step
     def push(self, feats, ended=None):
@@ -374,10 +392,10 @@ class StreamingRouter:
             self._advance(new_base - base, after[1] - new_base)
             self._base = new_base
         n_valid = ((self._len_dev + 3) // 4 - t0).clamp_(0, m).to(torch.int32)
-        labels, count = self._greedy(logits, n_valid)
+        labels, frames, count = self._greedy(logits, n_valid, t0)
         if self._beam is not None:
             self._beam.push(logits, n_valid)
             self._beam_best = None
         out = StreamOut(self, t0, logits)
-        self._pending.append((out, labels, count))
+        self._pending.append((out, labels, frames, count))
         return out

@@ -617,12 +617,14 @@ def process_valid_step(in_len_div, inputs, model, loss_state, blank_idx):
 
 
 @torch.no_grad()
-def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'):
+def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host', timestamps=False):
     """trainer_sr.py:96-117: forward, then tf.nn.ctc_beam_search_decoder(beam_width,
     top_paths=1) on the host (srf_amd.ctc.beam_search_decode) or, with
     decoder='device', on the GPU (srf_amd.ctc.beam_search_decode_device); best-path
     decoding when no beam width is configured.  Decode lengths use floor division, as
-    the reference does (:110)."""
+    the reference does (:110).  With timestamps=True returns (hyps, spans): per
+    utterance the (label, start, end) output-frame spans of its hypothesis, from
+    srf_amd.ctc.forced_align of the hypotheses against the same logits and lengths."""
     if decoder not in ('host', 'device'):
         raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
     feats, _, inp_len, _, utt_id = inputs
@@ -638,4 +640,6 @@ def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'
     for u, h in zip(utt_id, hyps):
         print('UTTID:', u)
         print(h)
+    if timestamps:
+        return hyps, ctc.forced_align(y_pred, lens, hyps, blank_index=y_pred.shape[-1] - 1).spans()
     return hyps
