@@ -431,6 +431,42 @@ int srf_ctc_align(const float* logits, const int* labels, const int* label_len, 
                   int C, int Lmax, int blank, int* states, int* tok_start, int* tok_end, float* tok_logp, float* score,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Scoring (the label error rate of an evaluation) ------------------------
+ * srf_edit_align: Levenshtein alignment, with a backtrace, of B hypotheses hyp [B][Hmax]
+ * against B references ref [B][Rmax] (int32 labels, dense, padded), hyp_len / ref_len [B]
+ * int32 clamped to [0, Hmax] / [0, Rmax]; entries past a length are never read.  All
+ * results are integers, so every output bit is defined.
+ * Fold (fold != NULL, fold [n_fold] int32): a label x becomes fold[x]; a label with
+ * fold[x] < 0 or x outside [0, n_fold) is dropped.  Both sequences are folded and
+ * compacted before the alignment (repeats are not merged); h [0, H) and r [0, R) are what
+ * is left.  fold = NULL (then n_fold = 0): labels are compared as they are.
+ * Distance: D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (h[i-1] != r[j-1]),
+ * D[i][j-1] + 1, D[i-1][j] + 1).  Backtrace: from (H, R), at every cell the first step
+ * that is consistent with D among (1) the diagonal, a correct label or a substitution,
+ * (2) the deletion (i, j) -> (i, j-1), a reference label without a hypothesis label,
+ * (3) the insertion (i, j) -> (i-1, j); i.e. on equal values the diagonal wins, then the
+ * deletion, then the insertion.  h = [1, 2], r = [2, 1] is two substitutions;
+ * h = [1, 1, 2], r = [1, 2] inserts h[0]; h = [1, 2], r = [1, 1, 2] deletes r[0].
+ * counts [B][6]: D[H][R], substitutions, deletions, insertions, R, H.
+ * hyp_to_ref [B][Hmax], ref_to_hyp [B][Rmax], indexed by the positions before the fold:
+ * the position (before the fold) of the partner for a correct or substituted label, -1
+ * for an inserted / deleted label, -2 for a label the fold dropped and for a position
+ * past the utterance's length.  Either map may be NULL.
+ * Accumulators, both optional and added to with 64-bit integer atomics (the caller zeroes
+ * them; the sums do not depend on the order): totals [8] = the sums of the six counts,
+ * the number of utterances, the number of utterances with D[H][R] > 0.  confusion
+ * [K + 1][K + 1] (1 <= K <= 32767), row the reference class and column the hypothesis
+ * class after the fold: the diagonal holds the correct labels, column K the deletions,
+ * row K the insertions, [K][K] stays 0; a pair with a class outside [0, K) is left out
+ * of confusion and still counts in totals.  Without confusion K is not used (K >= 0).
+ * 0 <= Hmax, Rmax <= 8192, B >= 1; anything else is refused before any launch (the
+ * workspace query then returns 0 and leaves a message).  workspace: 16-byte aligned,
+ * srf_edit_align_workspace bytes (never 0 for a legal shape). */
+size_t srf_edit_align_workspace(int B, int Hmax, int Rmax);
+int srf_edit_align(const int* hyp, const int* hyp_len, int Hmax, const int* ref, const int* ref_len, int Rmax, int B,
+                   const int* fold, int n_fold, int* counts, int* hyp_to_ref, int* ref_to_hyp, long long* totals,
+                   long long* confusion, int K, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- Chunked streaming inference (srf_amd/streaming.py) --------------------
  * srf_ctc_greedy_n: best-path decoding (per-frame arg-max, repeats merged, blanks
  * dropped; trainer_sr.py's greedy hypothesis) of one chunk of logits [B][n][C], of which

@@ -138,6 +138,9 @@ _SIGNATURES = {
     'srf_ctc_loss': (_c_int, [_vp] * 4 + [_c_int] * 5 + [ctypes.c_float, _vp, _vp, _vp, _c_size, _vp]),
     'srf_ctc_align_workspace': (_c_size, [_c_int] * 4),
     'srf_ctc_align': (_c_int, [_vp] * 4 + [_c_int] * 5 + [_vp] * 6 + [_c_size, _vp]),
+    'srf_edit_align_workspace': (_c_size, [_c_int] * 3),
+    'srf_edit_align': (_c_int, [_vp, _vp, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int] + [_vp] * 5
+                       + [_c_int, _vp, _c_size, _vp]),
     'srf_ctc_greedy_n': (_c_int, [_vp, _vp] + [_c_int] * 4 + [_vp, _vp, _vp, _vp]),
     'srf_ctc_greedy_frames_n': (_c_int, [_vp, _vp] + [_c_int] * 5 + [_vp, _vp, _vp, _vp, _vp]),
     'srf_ctc_beam_state_bytes': (_c_size, [_c_int] * 4),

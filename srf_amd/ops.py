@@ -576,6 +576,55 @@ def ctc_align(logits, labels, label_len, logit_len, blank):
     return states, tok_start, tok_end, tok_logp, score
 
 
+def _check_i32(name, t, shape):
+    if not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous int32 device tensor of shape {tuple(shape)}, got '
+                         f'{t.dtype} {tuple(t.shape)} on {t.device}')
+
+
+def edit_align(hyp, hyp_len, ref, ref_len, fold=None, maps=True, totals=None, confusion=None):
+    """srf_edit_align: Levenshtein alignment with a backtrace of hyp [B, Hmax] against ref
+    [B, Rmax] (int32 device tensors, lengths [B]), labels folded through fold [n_fold] when
+    given.  Returns device tensors (counts [B, 6], hyp_to_ref [B, Hmax], ref_to_hyp [B,
+    Rmax]) int32, the maps None with maps=False.  totals [8] and confusion [K + 1, K + 1]
+    (int64, on the device) are added to in the same launch."""
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp.shape[0] != ref.shape[0]:
+        raise ValueError(f'hyp and ref must be [B, Hmax] and [B, Rmax], got {tuple(hyp.shape)} and {tuple(ref.shape)}')
+    B, Hmax, Rmax = hyp.shape[0], hyp.shape[1], ref.shape[1]
+    _check_i32('hyp', hyp, (B, Hmax))
+    _check_i32('ref', ref, (B, Rmax))
+    _check_i32('hyp_len', hyp_len, (B,))
+    _check_i32('ref_len', ref_len, (B,))
+    if fold is not None:
+        _check_i32('fold', fold, (fold.numel(),))
+    K = 0
+    for name, t, nd in (('totals', totals, 1), ('confusion', confusion, 2)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int64 or t.dim() != nd or not t.is_contiguous()):
+            raise ValueError(f'{name} must be a contiguous int64 device tensor')
+    if totals is not None and totals.numel() != 8:
+        raise ValueError(f'totals must hold 8 sums, got {totals.numel()}')
+    if confusion is not None:
+        K = confusion.shape[0] - 1
+        if K < 1 or confusion.shape[1] != K + 1:
+            raise ValueError(f'confusion must be [K + 1, K + 1] with K >= 1, got {tuple(confusion.shape)}')
+    L = _lib.lib()
+    dev = hyp.device
+    wb = L.srf_edit_align_workspace(B, Hmax, Rmax)
+    if wb == 0:
+        _lib.check(-1, 'srf_edit_align_workspace')
+    counts = torch.empty((B, 6), device=dev, dtype=torch.int32)
+    h2r = torch.empty((B, Hmax), device=dev, dtype=torch.int32) if maps else None
+    r2h = torch.empty((B, Rmax), device=dev, dtype=torch.int32) if maps else None
+    ws = torch.empty(wb, device=dev, dtype=torch.uint8)
+
+    def opt(t):
+        return None if t is None else _ptr(t)
+    _lib.check(L.srf_edit_align(_ptr(hyp), _ptr(hyp_len), Hmax, _ptr(ref), _ptr(ref_len), Rmax, B, opt(fold),
+                                0 if fold is None else fold.numel(), _ptr(counts), opt(h2r), opt(r2h), opt(totals),
+                                opt(confusion), K, _ptr(ws), wb, _stream()), 'srf_edit_align')
+    return counts, h2r, r2h
+
+
 def ctc_greedy_frames_chunk(logits, n_valid, blank, prev, frame0):
     """srf_ctc_greedy_frames_n: ctc_greedy_chunk with the frame at which each label was
     emitted, counted from frame0 at the chunk's first frame.  Returns (labels [B, n]

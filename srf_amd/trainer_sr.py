@@ -605,29 +605,39 @@ def _check_faults(dev):
 
 
 @torch.no_grad()
-def process_valid_step(in_len_div, inputs, model, loss_state, blank_idx):
-    """trainer_sr.py:77-94."""
+def process_valid_step(in_len_div, inputs, model, loss_state, blank_idx, *, error_state=None):
+    """trainer_sr.py:77-94.  With error_state (a srf_amd.scoring.ErrorRate) the logits are
+    also decoded greedily on the device and scored against the labels there: two more
+    launches, no host synchronisation, and the loss is the bits it was."""
     feats, labels, inp_len, tar_len = inputs
     feats = _crop(feats, inp_len)
     y_pred = model(feats, input_lengths=inp_len, training=False)
-    pe_loss = ctc.ctc_loss(labels, y_pred, tar_len, ceil_div(inp_len, in_len_div), blank_index=blank_idx)
+    logit_len = ceil_div(inp_len, in_len_div)
+    pe_loss = ctc.ctc_loss(labels, y_pred, tar_len, logit_len, blank_index=blank_idx)
     if loss_state is not None:
         loss_state.update_state(pe_loss)
+    if error_state is not None:
+        prev = torch.full((y_pred.shape[0],), -1, dtype=torch.int32, device=y_pred.device)
+        hyp, count = ctc.greedy_decode_device(y_pred, logit_len, blank_idx, prev)
+        error_state.update_state(hyp, count, labels.to(y_pred.device), tar_len)
     return pe_loss
 
 
 @torch.no_grad()
-def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host', timestamps=False):
+def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host', timestamps=False, *,
+                      score=None):
     """trainer_sr.py:96-117: forward, then tf.nn.ctc_beam_search_decoder(beam_width,
     top_paths=1) on the host (srf_amd.ctc.beam_search_decode) or, with
     decoder='device', on the GPU (srf_amd.ctc.beam_search_decode_device); best-path
     decoding when no beam width is configured.  Decode lengths use floor division, as
     the reference does (:110).  With timestamps=True returns (hyps, spans): per
     utterance the (label, start, end) output-frame spans of its hypothesis, from
-    srf_amd.ctc.forced_align of the hypotheses against the same logits and lengths."""
+    srf_amd.ctc.forced_align of the hypotheses against the same logits and lengths.
+    With score (a srf_amd.scoring.ErrorRate) the hypotheses are also scored on the device
+    against the batch's labels and target lengths; what is printed and returned stays."""
     if decoder not in ('host', 'device'):
         raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
-    feats, _, inp_len, _, utt_id = inputs
+    feats, labels, inp_len, tar_len, utt_id = inputs
     feats = _crop(feats, inp_len)
     y_pred = model(feats, input_lengths=inp_len, training=False)
     lens = inp_len.to(torch.int64) // in_len_div
@@ -640,6 +650,8 @@ def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'
     for u, h in zip(utt_id, hyps):
         print('UTTID:', u)
         print(h)
+    if score is not None:
+        score.update_state(hyps, None, torch.as_tensor(labels).to(y_pred.device), tar_len)
     if timestamps:
         return hyps, ctc.forced_align(y_pred, lens, hyps, blank_index=y_pred.shape[-1] - 1).spans()
     return hyps
