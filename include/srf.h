@@ -466,6 +466,56 @@ size_t srf_edit_align_workspace(int B, int Hmax, int Rmax);
 int srf_edit_align(const int* hyp, const int* hyp_len, int Hmax, const int* ref, const int* ref_len, int Rmax, int B,
                    const int* fold, int n_fold, int* counts, int* hyp_to_ref, int* ref_to_hyp, long long* totals,
                    long long* confusion, int K, void* workspace, size_t workspace_bytes, void* stream);
+/* Words: a character model's labels cut at a separator label, and srf_edit_align's
+ * alignment over words instead of labels (the word error rate).  Everything is an integer
+ * except word_logp, so every output bit is defined.
+ * A dense int32 label row x[0, n), n = clamp(len, 0, Lmax); entries past n are never read.
+ * Position p is a separator if x[p] == sep (the raw label is tested before the fold, so a
+ * separator stays one whatever the fold says about it).  Otherwise, with a fold (fold
+ * [n_fold], srf_edit_align's table), p is dropped if x[p] is outside [0, n_fold) or
+ * fold[x[p]] < 0, else kept with class fold[x[p]]; without a fold p is kept with class x[p].
+ * A word is a maximal run of kept labels between separators: a dropped label neither
+ * splits a word nor adds to it (with n dropped, A n B is the word AB), and a run without a
+ * kept label is no word, so leading, trailing and repeated separators make none.  Word k,
+ * in order of appearance: start = the position (before the fold) of its first kept label,
+ * end = one past the position of its last, len = its kept labels.  At most (Lmax + 1) / 2.
+ * Two words are equal iff they have equal len and equal classes at every index (exact: a
+ * hash may only filter).  Ids: with the utterance's reference words r_0 .. r_{R-1}
+ * followed by its hypothesis words h_0 .. h_{H-1} as one list, a word's id is the index in
+ * that list of the first word equal to it: id(r_j) <= j; id(h_i) is a reference index if
+ * a reference word equals h_i, else R + i' for the first equal hypothesis word h_i'.
+ * The word alignment is srf_edit_align's definition on the two id rows: the same D, the
+ * same ties (diagonal, deletion, insertion), counts with R and H counted in words.
+ *
+ * srf_word_split: word_start / word_end [B][(Lmax + 1) / 2], -1 past word_count [B].
+ * tok_start / tok_end / tok_logp [B][Lmax] are srf_ctc_align's outputs for the same
+ * labels, all three or none.  With them word_frame_start = tok_start[start],
+ * word_frame_end = tok_end[end - 1], word_logp = the fp32 sum of tok_logp[p] over p in
+ * [start, end) in increasing p (one lane, sequentially: a float32 loop gives the same
+ * bits); -1 / -1 / 0 past the count and for an infeasible utterance (tok_start -1).
+ * Without them the three frame outputs are NULL.
+ *
+ * srf_word_align: counts [B][6] (required) and totals [8] (optional, 64-bit atomics) as
+ * srf_edit_align's, in words.  The per-word arrays, [B][(Hmax + 1) / 2] and
+ * [B][(Rmax + 1) / 2], hold -1 past the count; hyp_to_ref / ref_to_hyp, of the same
+ * widths and over word indices, hold -2 past the count and -1 for an inserted / deleted
+ * word.  Each per-word array may be NULL.  Two launches on the stream (the segmentation
+ * with the ids, then srf_edit_align's kernel on the ids), no host synchronisation and no
+ * allocation.  The id step compares a word with the words before it and is quadratic in
+ * the word count at worst.
+ * 0 <= Lmax, Hmax, Rmax <= 8192, B >= 1; anything else is refused before any launch (the
+ * workspace query then returns 0 and leaves a message).  workspace: 16-byte aligned, the
+ * query's bytes (never 0 for a legal shape). */
+size_t srf_word_split_workspace(int B, int Lmax);
+int srf_word_split(const int* labels, const int* label_len, int Lmax, int B, const int* fold, int n_fold, int sep,
+                   int* word_start, int* word_end, int* word_count, const int* tok_start, const int* tok_end,
+                   const float* tok_logp, int* word_frame_start, int* word_frame_end, float* word_logp,
+                   void* workspace, size_t workspace_bytes, void* stream);
+size_t srf_word_align_workspace(int B, int Hmax, int Rmax);
+int srf_word_align(const int* hyp, const int* hyp_len, int Hmax, const int* ref, const int* ref_len, int Rmax, int B,
+                   const int* fold, int n_fold, int sep, int* counts, int* hyp_word_start, int* hyp_word_end,
+                   int* hyp_word_id, int* ref_word_start, int* ref_word_end, int* ref_word_id, int* hyp_to_ref,
+                   int* ref_to_hyp, long long* totals, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- Chunked streaming inference (srf_amd/streaming.py) --------------------
  * srf_ctc_greedy_n: best-path decoding (per-frame arg-max, repeats merged, blanks

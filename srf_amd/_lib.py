@@ -141,6 +141,11 @@ _SIGNATURES = {
     'srf_edit_align_workspace': (_c_size, [_c_int] * 3),
     'srf_edit_align': (_c_int, [_vp, _vp, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int] + [_vp] * 5
                        + [_c_int, _vp, _c_size, _vp]),
+    'srf_word_split_workspace': (_c_size, [_c_int] * 2),
+    'srf_word_split': (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int] + [_vp] * 10 + [_c_size, _vp]),
+    'srf_word_align_workspace': (_c_size, [_c_int] * 3),
+    'srf_word_align': (_c_int, [_vp, _vp, _c_int, _vp, _vp, _c_int, _c_int, _vp, _c_int, _c_int] + [_vp] * 11
+                       + [_c_size, _vp]),
     'srf_ctc_greedy_n': (_c_int, [_vp, _vp] + [_c_int] * 4 + [_vp, _vp, _vp, _vp]),
     'srf_ctc_greedy_frames_n': (_c_int, [_vp, _vp] + [_c_int] * 5 + [_vp, _vp, _vp, _vp, _vp]),
     'srf_ctc_beam_state_bytes': (_c_size, [_c_int] * 4),

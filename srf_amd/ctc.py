@@ -103,6 +103,13 @@ class Alignment:
                 self._spans.append([(lab[k], st[k], en[k]) for k in range(n) if st[k] >= 0])
         return [list(s) for s in self._spans]
 
+    def words(self, separator, fold=None):
+        """The words of the aligned labels at the label ``separator`` with their frames
+        (srf_word_split; ``scoring.split_words`` with this alignment): a ``scoring.Words``
+        whose ``spans()`` are (labels tuple, start_frame, end_frame) per word."""
+        from . import scoring
+        return scoring.split_words(self.labels, self.label_lengths, separator, fold=fold, alignment=self)
+
 
 def forced_align(logits, logit_lengths, labels, label_lengths=None, blank_index=0):
     """CTC forced alignment on the device (srf_ctc_align): the most probable frame-level

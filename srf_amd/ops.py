@@ -625,6 +625,97 @@ def edit_align(hyp, hyp_len, ref, ref_len, fold=None, maps=True, totals=None, co
     return counts, h2r, r2h
 
 
+def _opt_ptr(t):
+    return None if t is None else _ptr(t)
+
+
+def word_split(labels, label_len, sep, fold=None, tok=None):
+    """srf_word_split: the words of labels [B, Lmax] (int32 device tensor, lengths [B]) at
+    the separator label sep, labels folded through fold [n_fold] when given.  Returns
+    device tensors (word_start, word_end [B, (Lmax + 1) // 2] int32, -1 past word_count [B]
+    int32) and, with tok = (tok_start, tok_end, tok_logp) of srf_ctc_align for the same
+    labels, (word_frame_start, word_frame_end int32, word_logp float32) of the same
+    width; None for the three without tok."""
+    if labels.dim() != 2:
+        raise ValueError(f'labels must be [B, Lmax], got {tuple(labels.shape)}')
+    B, Lmax = labels.shape
+    _check_i32('labels', labels, (B, Lmax))
+    _check_i32('label_len', label_len, (B,))
+    if fold is not None:
+        _check_i32('fold', fold, (fold.numel(),))
+    if tok is not None:
+        if len(tok) != 3 or any(t is None for t in tok):
+            raise ValueError('tok is the triple (tok_start, tok_end, tok_logp), all three or None')
+        _check_i32('tok_start', tok[0], (B, Lmax))
+        _check_i32('tok_end', tok[1], (B, Lmax))
+        _check_dev('tok_logp', tok[2], (B, Lmax))
+    L = _lib.lib()
+    dev = labels.device
+    wb = L.srf_word_split_workspace(B, Lmax)
+    if wb == 0:
+        _lib.check(-1, 'srf_word_split_workspace')
+    W = (Lmax + 1) // 2
+    start = torch.empty((B, W), device=dev, dtype=torch.int32)
+    end = torch.empty((B, W), device=dev, dtype=torch.int32)
+    count = torch.empty(B, device=dev, dtype=torch.int32)
+    fs = fe = lp = None
+    if tok is not None:
+        fs = torch.empty((B, W), device=dev, dtype=torch.int32)
+        fe = torch.empty((B, W), device=dev, dtype=torch.int32)
+        lp = torch.empty((B, W), device=dev, dtype=torch.float32)
+    ws = torch.empty(wb, device=dev, dtype=torch.uint8)
+    tk = (None, None, None) if tok is None else tok
+    _lib.check(L.srf_word_split(_ptr(labels), _ptr(label_len), Lmax, B, _opt_ptr(fold),
+                                0 if fold is None else fold.numel(), int(sep), _ptr(start), _ptr(end), _ptr(count),
+                                _opt_ptr(tk[0]), _opt_ptr(tk[1]), _opt_ptr(tk[2]), _opt_ptr(fs), _opt_ptr(fe),
+                                _opt_ptr(lp), _ptr(ws), wb, _stream()), 'srf_word_split')
+    return start, end, count, fs, fe, lp
+
+
+def word_align(hyp, hyp_len, ref, ref_len, sep, fold=None, words=True, maps=True, totals=None):
+    """srf_word_align: the words of hyp [B, Hmax] and ref [B, Rmax] (int32 device tensors,
+    lengths [B]) at the separator label sep, their ids, and srf_edit_align's alignment of
+    the id rows.  Returns device tensors (counts [B, 6], (start, end, id) of the hypothesis
+    words [B, (Hmax + 1) // 2], (start, end, id) of the reference words [B, (Rmax + 1) //
+    2], hyp_to_ref, ref_to_hyp over word indices) int32; the word tables are None with
+    words=False, the maps with maps=False.  totals [8] (int64, on the device) is added to
+    in the same call."""
+    if hyp.dim() != 2 or ref.dim() != 2 or hyp.shape[0] != ref.shape[0]:
+        raise ValueError(f'hyp and ref must be [B, Hmax] and [B, Rmax], got {tuple(hyp.shape)} and {tuple(ref.shape)}')
+    B, Hmax, Rmax = hyp.shape[0], hyp.shape[1], ref.shape[1]
+    _check_i32('hyp', hyp, (B, Hmax))
+    _check_i32('ref', ref, (B, Rmax))
+    _check_i32('hyp_len', hyp_len, (B,))
+    _check_i32('ref_len', ref_len, (B,))
+    if fold is not None:
+        _check_i32('fold', fold, (fold.numel(),))
+    if totals is not None and (not totals.is_cuda or totals.dtype != torch.int64 or totals.dim() != 1
+                               or not totals.is_contiguous()):
+        raise ValueError('totals must be a contiguous int64 device tensor')
+    if totals is not None and totals.numel() != 8:
+        raise ValueError(f'totals must hold 8 sums, got {totals.numel()}')
+    L = _lib.lib()
+    dev = hyp.device
+    wb = L.srf_word_align_workspace(B, Hmax, Rmax)
+    if wb == 0:
+        _lib.check(-1, 'srf_word_align_workspace')
+    WH, WR = (Hmax + 1) // 2, (Rmax + 1) // 2
+
+    def table(W, n):
+        return [torch.empty((B, W), device=dev, dtype=torch.int32) for _ in range(n)]
+    counts = torch.empty((B, 6), device=dev, dtype=torch.int32)
+    hw = table(WH, 3) if words else [None] * 3
+    rw = table(WR, 3) if words else [None] * 3
+    h2r = table(WH, 1)[0] if maps else None
+    r2h = table(WR, 1)[0] if maps else None
+    ws = torch.empty(wb, device=dev, dtype=torch.uint8)
+    _lib.check(L.srf_word_align(_ptr(hyp), _ptr(hyp_len), Hmax, _ptr(ref), _ptr(ref_len), Rmax, B, _opt_ptr(fold),
+                                0 if fold is None else fold.numel(), int(sep), _ptr(counts),
+                                *[_opt_ptr(t) for t in hw], *[_opt_ptr(t) for t in rw], _opt_ptr(h2r), _opt_ptr(r2h),
+                                _opt_ptr(totals), _ptr(ws), wb, _stream()), 'srf_word_align')
+    return counts, tuple(hw), tuple(rw), h2r, r2h
+
+
 def ctc_greedy_frames_chunk(logits, n_valid, blank, prev, frame0):
     """srf_ctc_greedy_frames_n: ctc_greedy_chunk with the frame at which each label was
     emitted, counted from frame0 at the chunk's first frame.  Returns (labels [B, n]

@@ -604,11 +604,17 @@ def _check_faults(dev):
         ops.check_faults()
 
 
+def _metrics(m):
+    """A metric (anything with ErrorRate's update_state) or a list / tuple of them."""
+    return list(m) if isinstance(m, (list, tuple)) else [m]
+
+
 @torch.no_grad()
 def process_valid_step(in_len_div, inputs, model, loss_state, blank_idx, *, error_state=None):
-    """trainer_sr.py:77-94.  With error_state (a srf_amd.scoring.ErrorRate) the logits are
-    also decoded greedily on the device and scored against the labels there: two more
-    launches, no host synchronisation, and the loss is the bits it was."""
+    """trainer_sr.py:77-94.  With error_state (a srf_amd.scoring.ErrorRate or
+    WordErrorRate, or a list / tuple of such metrics, each updated from the same
+    hypotheses) the logits are also decoded greedily on the device and scored against the
+    labels there: no host synchronisation, and the loss is the bits it was."""
     feats, labels, inp_len, tar_len = inputs
     feats = _crop(feats, inp_len)
     y_pred = model(feats, input_lengths=inp_len, training=False)
@@ -619,13 +625,14 @@ def process_valid_step(in_len_div, inputs, model, loss_state, blank_idx, *, erro
     if error_state is not None:
         prev = torch.full((y_pred.shape[0],), -1, dtype=torch.int32, device=y_pred.device)
         hyp, count = ctc.greedy_decode_device(y_pred, logit_len, blank_idx, prev)
-        error_state.update_state(hyp, count, labels.to(y_pred.device), tar_len)
+        for metric in _metrics(error_state):
+            metric.update_state(hyp, count, labels.to(y_pred.device), tar_len)
     return pe_loss
 
 
 @torch.no_grad()
 def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host', timestamps=False, *,
-                      score=None):
+                      score=None, word_separator=None, word_fold=None):
     """trainer_sr.py:96-117: forward, then tf.nn.ctc_beam_search_decoder(beam_width,
     top_paths=1) on the host (srf_amd.ctc.beam_search_decode) or, with
     decoder='device', on the GPU (srf_amd.ctc.beam_search_decode_device); best-path
@@ -633,10 +640,18 @@ def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'
     the reference does (:110).  With timestamps=True returns (hyps, spans): per
     utterance the (label, start, end) output-frame spans of its hypothesis, from
     srf_amd.ctc.forced_align of the hypotheses against the same logits and lengths.
-    With score (a srf_amd.scoring.ErrorRate) the hypotheses are also scored on the device
-    against the batch's labels and target lengths; what is printed and returned stays."""
+    With score (a srf_amd.scoring.ErrorRate or WordErrorRate, or a list / tuple of such
+    metrics) the hypotheses are also scored on the device against the batch's labels and
+    target lengths; what is printed and returned stays.  With timestamps=True and
+    word_separator (a label index; word_fold an optional fold table) returns (hyps, spans,
+    word_spans): per utterance the (labels tuple, start, end) output-frame spans of its
+    words (srf_amd.ctc.Alignment.words)."""
     if decoder not in ('host', 'device'):
         raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
+    if word_separator is None and word_fold is not None:
+        raise ValueError('word_fold comes with word_separator')
+    if word_separator is not None and not timestamps:
+        raise ValueError('word_separator asks for word times: it comes with timestamps=True')
     feats, labels, inp_len, tar_len, utt_id = inputs
     feats = _crop(feats, inp_len)
     y_pred = model(feats, input_lengths=inp_len, training=False)
@@ -651,7 +666,11 @@ def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'
         print('UTTID:', u)
         print(h)
     if score is not None:
-        score.update_state(hyps, None, torch.as_tensor(labels).to(y_pred.device), tar_len)
+        for metric in _metrics(score):
+            metric.update_state(hyps, None, torch.as_tensor(labels).to(y_pred.device), tar_len)
     if timestamps:
-        return hyps, ctc.forced_align(y_pred, lens, hyps, blank_index=y_pred.shape[-1] - 1).spans()
+        alignment = ctc.forced_align(y_pred, lens, hyps, blank_index=y_pred.shape[-1] - 1)
+        if word_separator is not None:
+            return hyps, alignment.spans(), alignment.words(word_separator, word_fold).spans()
+        return hyps, alignment.spans()
     return hyps
