@@ -567,6 +567,50 @@ int srf_ctc_beam_push_n(void* state, size_t state_bytes, int B, int C, int beam_
                         const float* logits, const int* n_valid, int n, int* frames_pushed, void* stream);
 int srf_ctc_beam_best(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int* labels,
                       int* count, float* log_prob, void* stream);
+/* srf_ctc_beam_nbest: the N most probable prefixes of each utterance in the beam's own
+ * rank order (total descending, then creation key ascending); row 0 is srf_ctc_beam_best's
+ * result bit for bit.  labels [B][N][max_len] (the first count entries of a row are
+ * written), count [B][N], log_prob [B][N] = log(p_b + p_nb), n_hyp [B] = min(N, beam
+ * entries).  Rows >= n_hyp[b] get count = 0 and log_prob = -inf.  A prefix longer than
+ * max_len gets count = -1 and no labels (its log_prob is set); max_len = max_frames
+ * always suffices.  One lane per (utterance, hypothesis) walks the trie; the state is not
+ * changed, so it may be called between pushes.  Refused before any launch unless
+ * 1 <= N <= beam_width and max_len >= 1. */
+int srf_ctc_beam_nbest(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int N,
+                       int max_len, int* labels, int* count, float* log_prob, int* n_hyp, void* stream);
+
+/* ---- MWER: expected error over an N-best list (tfsr/helper/train_helper.py
+ * loss_ewerr) ----------------------------------------------------------------
+ * logits [B][Tmax][C] and logit_len [B] as srf_ctc_loss's (T_b = clamp(logit_len[b], 0,
+ * Tmax)); hyp [B][N][Lmax] int32 dense label rows, hyp_len [B][N] clamped to [0, Lmax]
+ * (entries past a length are never read), n_hyp [B] clamped to [0, N], err [B][N] int32
+ * error counts.  With lp = log_softmax in fp32, per utterance over its n = n_hyp[b] rows:
+ *   ll_i = log P_CTC(y_i | x), the full sum over alignments (-nll of srf_ctc_loss; an
+ *          empty row is legal; -inf if infeasible, if T_b = 0 or if a label lies outside
+ *          [0, C)),
+ *   p_i = exp(ll_i - LSE_k ll_k), ebar = (sum_i e_i) / n, loss_b = sum_i p_i (e_i - ebar),
+ *   w_i = p_i (e_i - ebar - loss_b) = d loss_b / d ll_i,
+ *   grad[b][t][c] = grad_scale * sum_i w_i occ_i[t][c] for t < T_b, 0 past T_b, where
+ *   occ_i is hypothesis i's state occupancy exp(LSE_{s: ext_i[s] = c}(alpha_i + beta_i)
+ *   - lp - ll_i).  sum_i w_i = 0, so every row of grad sums to 0 over c.
+ * e_i - ebar is computed as (n e_i - sum e) / n: equal errors (and n = 1) give loss = 0
+ * and grad = 0 exactly.  n = 0 or every ll_i = -inf: loss = 0, grad = 0, p = 0.
+ * Outputs: hyp_logp [B][N] = ll_i (-inf past n_hyp), p_hat [B][N], loss [B], grad
+ * [B][Tmax][C] (NULL: loss only, the same bits).  Four launches on the stream, no
+ * allocation, no host synchronisation: the log-softmax once per utterance, the alpha /
+ * beta recursions of all B N hypotheses in one launch, p / loss / w, the gradient.
+ * Limits: B >= 1, 1 <= Tmax <= 65535, C >= 2, 0 <= blank < C, 1 <= N <= SRF_MWER_MAX_HYP,
+ * Lmax >= 0 with 12 (2 Lmax + 1) <= 65536 and 4 (2 C + 3 Lmax + 1) <= 65536 (LDS bytes),
+ * B N < 2^31, Tmax (2 Lmax + 1) <= 2^29; anything else is refused before any launch (the
+ * workspace query then returns 0 and leaves a message).  workspace: 16-byte aligned,
+ *   srf_mwer_workspace = 4 (B Tmax C + B N Tmax 2 (2 Lmax + 1) + B N) bytes
+ * (log-softmax, alpha and beta of every hypothesis, w). */
+#define SRF_MWER_MAX_HYP 32
+size_t srf_mwer_workspace(int B, int Tmax, int C, int N, int Lmax);
+int srf_mwer_loss(const float* logits, const int* logit_len, const int* hyp, const int* hyp_len, const int* n_hyp,
+                  const int* err, int B, int Tmax, int C, int N, int Lmax, int blank, float grad_scale,
+                  float* hyp_logp, float* p_hat, float* loss, float* grad, void* workspace, size_t workspace_bytes,
+                  void* stream);
 /* srf_stream_advance_n: up to SRF_STREAM_ADVANCE_MAX sliding state buffers, each
  * [B][rows_per_stream][row_bytes], move rows [shift, shift + keep) of every stream to
  * rows [0, keep) in one launch (the other rows keep or lose their content: undefined).

@@ -479,6 +479,46 @@ __global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __res
   log_prob[b] = best_tot;
 }
 
+// The N first beam entries of each utterance.  After a frame the beam lies in rank order
+// (total descending, creation key ascending), so hypothesis i is slot i; before the first
+// frame the root is the only entry.  The walk from a node to the root follows parent
+// pointers and is serial, so a lane walks one hypothesis: a wave holds 64 (utterance,
+// hypothesis) pairs, every lane on its own trie path.  Grid (B, ceil(N / 64)).
+__global__ __launch_bounds__(64) void ctc_beam_nbest_kernel(const unsigned* __restrict__ state, int W, int max_frames,
+                                                            int N, int max_len, int* __restrict__ labels,
+                                                            int* __restrict__ count, float* __restrict__ log_prob,
+                                                            int* __restrict__ n_hyp) {
+  const int b = blockIdx.x, i = blockIdx.y * 64 + threadIdx.x;
+  if (i >= N) return;
+  const size_t cap = trie_capacity(W, max_frames);
+  const unsigned* st = state + (size_t)b * state_words(W, max_frames);
+  const int* hdr = reinterpret_cast<const int*>(st);
+  const unsigned* beam = st + kHeader;
+  const int* trie_parent = reinterpret_cast<const int*>(beam + (size_t)kFields * W);
+  const int* trie_label = trie_parent + cap;
+  const int nb = min(max(hdr[0], 1), W);
+  if (i == 0) n_hyp[b] = min(N, nb);
+  const size_t row = (size_t)b * N + i;
+  if (i >= nb) {
+    count[row] = 0;
+    log_prob[row] = neg_inf();
+    return;
+  }
+  log_prob[row] = log_sum_exp(__uint_as_float(beam[W + i]), __uint_as_float(beam[2 * W + i]));
+  const int len = min(max((int)beam[4 * W + i], 0), max_frames);
+  if (len > max_len) {
+    count[row] = -1;
+    return;
+  }
+  int* out = labels + row * max_len;
+  int node = (int)beam[i];
+  for (int k = len - 1; k >= 0 && node > 0 && (size_t)node < cap; --k) {
+    out[k] = trie_label[node];
+    node = trie_parent[node];
+  }
+  count[row] = len;
+}
+
 bool shape_ok(int B, int C, int W, int max_frames) {
   return B >= 1 && C >= 2 && C <= kMaxC && W >= 1 && W <= kMaxW && max_frames >= 1 &&
          state_words(W, max_frames) <= (size_t)0x7fffffff;
@@ -550,5 +590,23 @@ extern "C" int srf_ctc_beam_best(const void* state, size_t state_bytes, int B, i
   hipLaunchKernelGGL(ctc_beam_best_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned*>(state), beam_width, max_frames, labels, count, log_prob);
   SRF_LAUNCH_CHECK("ctc_beam_best");
+  return SRF_OK;
+}
+
+extern "C" int srf_ctc_beam_nbest(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                  int N, int max_len, int* labels, int* count, float* log_prob, int* n_hyp,
+                                  void* stream) {
+  SRF_BEAM_SHAPE("ctc_beam_nbest");
+  SRF_REQUIRE(N >= 1 && N <= beam_width && max_len >= 1,
+              "ctc_beam_nbest: need 1 <= N <= beam_width and max_len >= 1 (N=%d beam_width=%d max_len=%d)", N,
+              beam_width, max_len);
+  SRF_REQUIRE(state && labels && count && log_prob && n_hyp, "ctc_beam_nbest: null pointer argument");
+  SRF_REQUIRE(state_bytes >= (size_t)B * state_words(beam_width, max_frames) * 4,
+              "ctc_beam_nbest: the state block holds %zu bytes, %zu are needed", state_bytes,
+              (size_t)B * state_words(beam_width, max_frames) * 4);
+  hipLaunchKernelGGL(ctc_beam_nbest_kernel, dim3((unsigned)B, (unsigned)((N + 63) / 64)), dim3(64), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned*>(state), beam_width, max_frames, N,
+                     max_len, labels, count, log_prob, n_hyp);
+  SRF_LAUNCH_CHECK("ctc_beam_nbest");
   return SRF_OK;
 }

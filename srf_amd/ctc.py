@@ -204,6 +204,59 @@ class BeamState:
         return [labels[b][:count[b]] for b in range(self.shape[0])], log_prob.cpu().double().numpy()
 
 
+    def nbest(self, n, max_len=None):
+        """The ``n`` most probable prefixes of every utterance so far, in the beam's rank
+        order (srf_ctc_beam_nbest), as an ``NBest`` on the device; the state stays as it
+        is.  1 <= n <= beam_width.  ``max_len`` bounds the label rows (a longer prefix
+        gets length -1); None takes max_frames, which always suffices."""
+        if not 1 <= int(n) <= self.shape[2]:
+            raise ValueError(f'n must lie in 1 .. beam_width = {self.shape[2]}, got {n}')
+        max_len = self.shape[3] if max_len is None else int(max_len)
+        if max_len < 1:
+            raise ValueError(f'max_len must be at least 1, got {max_len}')
+        return NBest(*ops.ctc_beam_nbest(self._state, self.shape, int(n), max_len))
+
+
+class NBest:
+    """N-best list of a device beam search, all on the device: ``labels`` [B, N, max_len]
+    int32 (the first ``lengths`` entries of a row are defined), ``lengths`` [B, N] int32
+    (0 past ``count``; -1 for a prefix longer than max_len), ``log_prob`` [B, N] float32
+    (the beam's log(p_b + p_nb), non-increasing along N, -inf past ``count``) and
+    ``count`` [B] int32, the hypotheses the beam held (at most N).  ``lists()`` is the
+    host view."""
+
+    def __init__(self, labels, lengths, log_prob, count):
+        self.labels, self.lengths, self.log_prob, self.count = labels, lengths, log_prob, count
+
+    def lists(self):
+        """Per utterance a list of (label list, log probability), ``count`` long.  One
+        copy to the host."""
+        B, N, Lmax = self.labels.shape
+        packed = torch.cat([self.labels.reshape(B, N * Lmax), self.lengths, self.count[:, None]], dim=1).cpu().tolist()
+        logp = self.log_prob.cpu().double().tolist()
+        out = []
+        for row, lp in zip(packed, logp):
+            lens, n = row[N * Lmax:N * Lmax + N], row[-1]
+            out.append([(row[i * Lmax:i * Lmax + max(lens[i], 0)], lp[i]) for i in range(n)])
+        return out
+
+
+def beam_search_nbest_device(logits, lengths, blank_index, beam_width, n):
+    """The ``n`` best prefixes of a device beam search over logits [B, T, C] (one reset,
+    one push, one N-best call), as an ``NBest`` on the device: nothing is copied to the
+    host.  ValueError outside 2 <= C <= 128, 1 <= n <= beam_width <= 128."""
+    if not torch.is_tensor(logits) or logits.dim() != 3 or not logits.is_cuda:
+        shape, where = tuple(getattr(logits, 'shape', ())), getattr(logits, 'device', 'the host')
+        raise ValueError(f'logits must be a device tensor [B, T, C], got {shape} on {where}')
+    B, T, C = logits.shape
+    _check_beam_range(C, blank_index, beam_width)
+    if B < 1:
+        raise ValueError('logits hold no utterance')
+    state = BeamState(B, C, blank_index, beam_width, max(T, 1), logits.device)
+    state.push(logits, torch.as_tensor(lengths))
+    return state.nbest(n)
+
+
 def beam_search_decode_device(logits, lengths, blank_index, beam_width=100):
     """beam_search_decode on the device: one reset, one push and one best call of the HIP
     prefix beam search; the labels, counts and scores are copied to the host, the logits

@@ -801,6 +801,60 @@ def ctc_beam_best(state, shape):
     return labels, count, log_prob
 
 
+def ctc_beam_nbest(state, shape, n, max_len, labels=None):
+    """srf_ctc_beam_nbest: the n first prefixes of every beam in rank order, on the device:
+    (labels [B, n, max_len] int32, count [B, n] int32, log_prob [B, n] float32, n_hyp [B]
+    int32).  Only the first count entries of a label row are written (into ``labels`` when
+    a buffer of that shape is given); count is -1 for a prefix longer than max_len.  The
+    state is left as it is."""
+    B = shape[0]
+    n, max_len = int(n), int(max_len)
+    dev = state.device
+    if labels is None:
+        labels = torch.empty((B, max(n, 0), max(max_len, 0)), device=dev, dtype=torch.int32)
+    else:
+        _check_i32('labels', labels, (B, n, max_len))
+    count = torch.empty((B, max(n, 0)), device=dev, dtype=torch.int32)
+    log_prob = torch.empty((B, max(n, 0)), device=dev, dtype=torch.float32)
+    n_hyp = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.check(_lib.lib().srf_ctc_beam_nbest(*_beam_state_args(state, shape), n, max_len, _ptr(labels), _ptr(count),
+                                             _ptr(log_prob), _ptr(n_hyp), _stream()), 'srf_ctc_beam_nbest')
+    return labels, count, log_prob, n_hyp
+
+
+def mwer_loss_and_grad(logits, logit_len, hyp, hyp_len, n_hyp, err, blank, grad_scale, want_grad=True):
+    """srf_mwer_loss: the expected error of each utterance over its hypothesis list and
+    grad_scale * its logit gradient.  logits [B, T, C] float32, logit_len [B], hyp
+    [B, N, Lmax], hyp_len [B, N], n_hyp [B], err [B, N] (int32, all on the device).
+    Returns device tensors (loss [B], grad [B, T, C] or None with want_grad=False, p_hat
+    [B, N], hyp_logp [B, N])."""
+    if logits.dim() != 3 or hyp.dim() != 3 or hyp.shape[0] != logits.shape[0]:
+        raise ValueError(f'logits must be [B, T, C] and hyp [B, N, Lmax], got {tuple(logits.shape)} and '
+                         f'{tuple(hyp.shape)}')
+    B, T, C = logits.shape
+    N, Lmax = hyp.shape[1], hyp.shape[2]
+    _check_dev('logits', logits, (B, T, C))
+    _check_i32('logit_len', logit_len, (B,))
+    _check_i32('hyp', hyp, (B, N, Lmax))
+    _check_i32('hyp_len', hyp_len, (B, N))
+    _check_i32('n_hyp', n_hyp, (B,))
+    _check_i32('err', err, (B, N))
+    L = _lib.lib()
+    dev = logits.device
+    wb = L.srf_mwer_workspace(B, T, C, N, Lmax)
+    if wb == 0:
+        _lib.check(-1, 'srf_mwer_workspace')
+    hyp_logp = torch.empty((B, N), device=dev, dtype=torch.float32)
+    p_hat = torch.empty((B, N), device=dev, dtype=torch.float32)
+    loss = torch.empty(B, device=dev, dtype=torch.float32)
+    grad = torch.empty((B, T, C), device=dev, dtype=torch.float32) if want_grad else None
+    ws = torch.empty(wb, device=dev, dtype=torch.uint8)
+    _lib.check(L.srf_mwer_loss(_ptr(logits.detach()), _ptr(logit_len), _ptr(hyp), _ptr(hyp_len), _ptr(n_hyp),
+                               _ptr(err), B, T, C, N, Lmax, int(blank), float(grad_scale), _ptr(hyp_logp), _ptr(p_hat),
+                               _ptr(loss), _opt_ptr(grad), _ptr(ws), wb, _stream()), 'srf_mwer_loss')
+    return loss, grad, p_hat, hyp_logp
+
+
 def stream_advance(bufs):
     """srf_stream_advance_n: bufs = [(tensor [B, rows, ...], rows, shift, keep)]; rows
     [shift, shift + keep) of every stream of every tensor move to rows [0, keep), in

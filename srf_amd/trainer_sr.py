@@ -284,6 +284,76 @@ def process_train_step(in_len_div, inputs, model, optimizer, loss_state, frame_s
     return pe_loss
 
 
+class MwerOptions:
+    """What ``process_train_step_mwer`` needs beyond ``process_train_step``'s arguments:
+    ``n_best`` hypotheses taken from a device beam search of width ``beam_width``, the
+    weight ``ctc_weight`` of the reference labels' CTC loss that is added to the expected
+    error, and how errors are counted: in words parted by the label ``separator`` when it
+    is given, else in labels; ``fold`` is an optional ``scoring.fold_table``.  A trainer
+    that parses --train-is-mwer passes ``MwerOptions(...)`` as ``distributed_train_step``'s
+    ``mwer`` when the flag is set and None otherwise."""
+
+    def __init__(self, n_best=4, beam_width=16, ctc_weight=0.01, separator=None, fold=None):
+        if not 1 <= int(n_best) <= 32:
+            raise ValueError(f'n_best must lie in 1 .. 32, got {n_best}')
+        if not int(n_best) <= int(beam_width) <= ctc.BEAM_MAX_WIDTH:
+            raise ValueError(f'beam_width must lie in n_best .. {ctc.BEAM_MAX_WIDTH}, got {beam_width}')
+        if float(ctc_weight) < 0:
+            raise ValueError(f'ctc_weight must not be negative, got {ctc_weight}')
+        self.n_best, self.beam_width, self.ctc_weight = int(n_best), int(beam_width), float(ctc_weight)
+        self.separator, self.fold = separator, fold
+
+
+def process_train_step_mwer(in_len_div, inputs, model, optimizer, loss_state, frame_state, n_gpus, blank_idx, samples,
+                            options, error_state=None):
+    """process_train_step with the MWER loss (srf_amd.mwer; train_helper.py's loss_ewerr):
+    one training forward; on its logits a device beam search, the ``options.n_best`` best
+    prefixes, their error counts against the labels and the expected error with its logit
+    gradient (scaled by 1 / (B n_gpus)); plus ``options.ctc_weight`` times the CTC loss of
+    the labels and its gradient; then the backward, the reduction and the optimizer as in
+    process_train_step.  Returns (and reports to ``loss_state``) the per-utterance
+    loss_mwer + ctc_weight * nll.  ``error_state`` (a scoring.ErrorRate / WordErrorRate or
+    a list of them) is updated from hypothesis 0, the beam's best.  Nothing between the
+    forward and the optimizer copies to the host or synchronises."""
+    from . import mwer
+    feats, labels, inp_len, tar_len = inputs
+    batch = feats.shape[0]
+    feats = _crop(feats, inp_len)
+    host_len = inp_len
+    inp_len = inp_len.to(feats.device, non_blocking=True)
+    b = getattr(model, 'grad_buckets', None)
+    if b is not None:
+        b.begin()
+    y_pred = model(feats, input_lengths=inp_len, training=True)
+    logit_len = ceil_div(inp_len, in_len_div)
+    scale = 1.0 / float(batch * n_gpus)
+    with torch.no_grad():
+        logits = y_pred.detach()
+        nbest = ctc.beam_search_nbest_device(logits, logit_len, blank_idx, options.beam_width, options.n_best)
+        errors = mwer.hypothesis_errors(nbest, labels, tar_len, options.separator, options.fold)
+        pe_loss, g_logits, _, _ = mwer.mwer_loss_and_grad(logits, logit_len, nbest, errors, blank_idx, scale)
+        if options.ctc_weight > 0:
+            nll, g_ctc = ctc.ctc_loss_and_grad(labels, y_pred, tar_len, logit_len, blank_idx,
+                                               options.ctc_weight * scale)
+            pe_loss = pe_loss + options.ctc_weight * nll
+            g_logits = g_logits + g_ctc
+    y_pred.backward(g_logits)
+    ops.dr_side_join()
+    _reduce(model)
+    optimizer.apply_gradients(model)
+    if error_state is not None:
+        for metric in _metrics(error_state):
+            metric.update_state(nbest.labels[:, 0, :].contiguous(), nbest.lengths[:, 0].contiguous(),
+                                labels.to(y_pred.device), tar_len)
+    if loss_state is not None:
+        loss_state.update_state(pe_loss)
+    if frame_state is not None:
+        frame_state.update_state(host_len.sum())
+    if samples is not None:
+        samples.update_state(batch)
+    return pe_loss
+
+
 _SEED_COUNTERS = {}
 
 
@@ -567,19 +637,26 @@ def batch_to_device(batch, dev):
 
 
 def distributed_train_step(dataset, in_len_div, model, optimizer, loss_state, frame_state, n_gpus, blank_idx,
-                           samples, train_num=None, graphs=None, log=print):
+                           samples, train_num=None, graphs=None, log=print, mwer=None):
     """trainer_sr.py:205-222 (the hot loop): every batch of this replica's
     dataset (data_helper.create_ds_for_training(..., rank, world)) through one
     training step, with the reference's progress line every 50 steps.  ``graphs``
     (a GraphCache) replays a captured step per batch shape; None runs
-    process_train_step eagerly."""
+    process_train_step eagerly.  ``mwer`` (a MwerOptions; the reference's
+    --train-is-mwer) runs process_train_step_mwer instead; the MWER step is not
+    captured, so it does not go with ``graphs``."""
+    if mwer is not None and graphs is not None:
+        raise ValueError('the MWER step is not captured into a graph: pass graphs=None with mwer')
     dev = model.flat_params.device
     index = 0
     if log is not None:
         log('Step, Progress%, Average Loss, lr')
     for example in dataset:
         inputs = batch_to_device(example, dev)
-        if graphs is None:
+        if mwer is not None:
+            process_train_step_mwer(in_len_div, inputs, model, optimizer, loss_state, frame_state, n_gpus, blank_idx,
+                                    samples, mwer)
+        elif graphs is None:
             process_train_step(in_len_div, inputs, model, optimizer, loss_state, frame_state, n_gpus, blank_idx,
                                samples)
         else:
