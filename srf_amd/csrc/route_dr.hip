@@ -864,6 +864,12 @@ __global__ __launch_bounds__(256, DIN >= 32 ? (R >= 4 ? 2 : 3) : (R >= 4 ? 3 : 4
 #ifndef SRF_GW16S_XCD
 #define SRF_GW16S_XCD 1
 #endif
+// route_gw16s_kernel's per-frame vector path (its VW): 0 = 4-byte loads per lane,
+// 2 = 16-byte loads through an LDS image shared by two waves (1, a wave-private image,
+// lost to 0 and is gone)
+#ifndef SRF_GW16S_LDSVEC
+#define SRF_GW16S_LDSVEC 2
+#endif
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -1636,39 +1642,56 @@ __global__ __launch_bounds__(256, (D >= 32 && CAP >= 8) ? 2 : 3) void route_gw3_
 //     step (x1 g1 + x1 g2 + x2 g1, the dropped x2 g2 <= 2^-21 |x' gu'|), scaled back by
 //     2^-(bx + eg) once at the end.  Errors are absolute at the layer's scale (below
 //     2^-24 of max|x'| max|gu'| per product), as in the forward's per-tensor split.
-// Workgroup = 4 waves x 32 rows (one output capsule j each) x CAP capsules x one of S
-// frame splits; lane l holds row 32j + (l & 31) and frames 8(l >> 5) + 0..7 of each
-// K step (B map), e = 8q + 4(l >> 5) + 0..3 of its C map.  Tile t + 1's couplings and
-// x planes are staged while tile t computes (one barrier per tile), the per-frame
-// vectors one tile ahead in registers.  LDS x planes: row e = 16 halves = two 8-half
-// chunks, chunk c of row e at c ^ ((e >> 3) & 1): the ds_read_b128 lane groups then
-// cover 64 distinct banks.
+// Workgroup = 4 waves x 32 rows (one output capsule j each) x one or two groups of CAP
+// capsules x one of S frame splits; lane l holds row 32j + (l & 31) and frames
+// 8(l >> 5) + 0..7 of each K step (B map), e = 8q + 4(l >> 5) + 0..3 of its C map.
+// Tile t + 1's couplings and x planes are staged while tile t computes (one barrier per
+// tile).  LDS x planes: row e = 16 halves = two 8-half chunks, chunk c of row e at
+// c ^ ((e >> 3) & 1): the ds_read_b128 lane groups then cover 64 distinct banks.
+// VW: how the per-frame vectors gs^r, Vc^r reach the lanes (the B map wants 8 frames of
+// one row, the arrays are [F][J dout]).
+//   0: forty 4-byte buffer loads per tile and lane, one tile ahead in registers;
+//      workgroup = 4 waves, one capsule group.
+//   2: workgroup = 8 waves, 4 j x 2 adjacent capsule groups.  The two waves of a j load
+//      half a tile of its vectors each with 16-byte loads along the rows (a float4 = 4
+//      rows of one frame: frame 8g + (l >> 3), rows 4(l & 7) + 0..3 for capsule group g),
+//      two tiles ahead, and write them transposed to the j's LDS image
+//      [vector][row][16 frames], double-buffered over the tile barrier; both read their
+//      lane's 8 frames back with two ds_read_b128 per vector.  Image row n keeps its
+//      16-byte slot s at s ^ ((n >> 2) & 3): the ds_read_b128 lane groups cover 64
+//      distinct banks, the 32-lane halves of a ds_write_b32 hit each bank twice (free).
+//      A tile's image stores are spread over its capsules, behind each one's MFMAs.
 constexpr int kGw16Cap = 4;
-template <int R, int CAP>
-__global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
+template <int R, int CAP, int VW>
+__global__ __launch_bounds__(VW == 2 ? 512 : 256, 2) void route_gw16s_kernel(
     const _Float16* __restrict__ x16, const float* __restrict__ hdr, const float* __restrict__ gumax,
     const float* __restrict__ saved, const float* __restrict__ gs, const float* __restrict__ cst,
     const float* __restrict__ glst, int F, int Fp, int in_n, int J, int mask_first, int JP, int n_rt, int S,
     int ft_per, float* __restrict__ gwp, float* __restrict__ gbp, size_t pstride) {
   static_assert(R >= 2 && R <= 3, "stored couplings exist for iters >= 2; registers hold R <= 3");
-  constexpr int D = 32, RV = R - 1;
+  static_assert(VW == 0 || VW == 2, "0: per-lane loads, 2: image shared by two waves");
+  constexpr int D = 32, RV = R - 1, NV = R + RV;
+  constexpr int NG = VW == 2 ? 2 : 1;    // capsule groups per workgroup
+  constexpr int NT = 256 * NG, CAPW = CAP * NG;
   constexpr int CG = RV * 2 * 4 * 16;    // couplings per capsule: [r][c|gl][4 j][16 frames] floats
   constexpr int PQ = CG / 4 + 128;       // 16-byte pieces staged per capsule (couplings + x hi/lo)
   constexpr int PCB = CG * 4 + 2 * D * 16 * 2;   // LDS bytes per capsule: couplings, x hi, x lo
-  constexpr int NQ = (CAP * PQ + 255) / 256;
-  __shared__ __attribute__((aligned(16))) unsigned char stg[2][CAP * PCB];
+  constexpr int NQ = (CAPW * PQ + NT - 1) / NT;
+  constexpr int IMG = NV * D * 16;       // floats of one output capsule's vector image
+  __shared__ __attribute__((aligned(16))) unsigned char stg[2][CAPW * PCB];
+  __shared__ __attribute__((aligned(16))) float vimg[VW == 0 ? 4 : 2 * 4 * IMG];   // VW 2: [buffer][j]
   const int JD = J * D;
   const size_t FJD = (size_t)F * JD;
   const int Fs = srf::fwd32_frame_stride(F);
   const size_t cblk = (size_t)in_n * JP * Fs;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63, wv = (threadIdx.x >> 6) & 3, wg = threadIdx.x >> 8;
   const int n = lane & 31, h = lane >> 5;
 #if SRF_GW16S_XCD
   // XCD-aware task order (as route_gux16_kernel): XCD x takes the x-th eighth of the
   // tasks ordered capsule group fastest, then output-capsule group, then frame split, so
   // a (split, group)'s gs^r / Vc^r rows stay on one XCD and a split's x planes on the
   // two or three XCDs that cover it (they were read on all eight)
-  const int n_cc = (in_n + CAP - 1) / CAP, n_tasks = n_cc * n_rt * S;
+  const int n_cc = (in_n + CAPW - 1) / CAPW, n_tasks = n_cc * n_rt * S;
   const int task = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
   if (task >= n_tasks) return;
   const int cc = task % n_cc;
@@ -1687,7 +1710,8 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
   const int row = j * D + n;
   const int Jeff = J - (mask_first ? 1 : 0);
   const float c0 = (wave_on && !(mask_first && j == 0)) ? 1.f / (float)Jeff : 0.f;
-  const int i0 = cc * CAP, ncap = min(in_n, i0 + CAP) - i0;
+  // the workgroup's capsules i0 + 0 .. ncap - 1; the wave's are k0 + 0 .. CAP - 1 of them
+  const int i0 = cc * CAPW, ncap = min(in_n, i0 + CAPW) - i0, k0 = wg * CAP;
   const int NFT = Fp >> 4;
   const int ft0 = s * ft_per, ft1 = min(NFT, ft0 + ft_per);
   const int bx = (int)hdr[2];
@@ -1697,15 +1721,15 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
   // staging: 16-byte piece q of a tile <-> (capsule k, part): couplings (r, c|gl, jq,
   // frame quad) or an x chunk (plane, e, 8-frame half); per-thread sources fixed, the
   // next tile is 64 bytes (couplings) or 2 KiB (x planes) on
-  constexpr int NCPL = CAP * CG / 4;
+  constexpr int NCPL = CAPW * CG / 4;
   const char* src[NQ];
   int dst[NQ];
   bool cpl[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-    const int idx = min(q * 256 + (int)threadIdx.x, CAP * PQ - 1);
-    // known at compile time wherever a round of 256 pieces is all couplings or all x
-    cpl[q] = (q + 1) * 256 <= NCPL || (q * 256 < NCPL && idx < NCPL);
+    const int idx = min(q * NT + (int)threadIdx.x, CAPW * PQ - 1);
+    // known at compile time wherever a round of NT pieces is all couplings or all x
+    cpl[q] = (q + 1) * NT <= NCPL || (q * NT < NCPL && idx < NCPL);
     if (cpl[q]) {
       const int k = idx / (CG / 4), rem = idx - k * (CG / 4);
       const int i = i0 + min(k, ncap - 1);
@@ -1730,8 +1754,8 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
   auto stage_store = [&](int buf) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-      const int idx = q * 256 + threadIdx.x;
-      if ((CAP * PQ) % 256 != 0 && idx >= CAP * PQ) continue;
+      const int idx = q * NT + threadIdx.x;
+      if ((CAPW * PQ) % NT != 0 && idx >= CAPW * PQ) continue;
       // couplings go to LDS as c 2^eg, gL 2^eg (exact): the tile loop then scales no vector
       *reinterpret_cast<f4*>(&stg[buf][dst[q]]) = cpl[q] ? sv[q] * sg : sv[q];
     }
@@ -1747,11 +1771,11 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
                                                       (int)nrec, 0x00020000);
   }
   const uint32_t vo0 = (uint32_t)((8 * h) * JD + row) * 4;
-  // per-frame vectors as frame pairs, in two register sets: a tile computes from one
-  // while the next tile's loads land in the other (the tile loop is unrolled by two), so
-  // no vector is copied or rescaled; only gs^0 takes its factor c^0 2^eg per tile
-  f2 nxa[R + RV][4], nxb[R + RV][4];
-  auto vec_load = [&](f2 (&nx)[R + RV][4], int ft) {
+  // VW 0: per-frame vectors as frame pairs, in two register sets: a tile computes from
+  // one while the next tile's loads land in the other (the tile loop is unrolled by two),
+  // so no vector is copied or rescaled; only gs^0 takes its factor c^0 2^eg per tile
+  f2 nxa[NV][4], nxb[NV][4];
+  auto vec_load = [&](f2 (&nx)[NV][4], int ft) {
 #pragma unroll
     for (int v = 0; v < 8; ++v) {
       const uint32_t so = (uint32_t)((ft * 16 + v) * JD) * 4;
@@ -1762,6 +1786,33 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
       }
     }
   };
+  // VW 2: the wave's half of its j's vectors for a tile (frames 8 wg + 0..7), held raw
+  // until it goes to the image; the image read back as the lane's frame pairs
+  const int rq = lane & 7, fm = lane >> 3;
+  const uint32_t wo0 = (uint32_t)((8 * wg + fm) * JD + j * D + 4 * rq) * 4;
+  f4 vst[NV];
+  auto img_load = [&](int ft) {
+    const uint32_t so = (uint32_t)(ft * 16 * JD) * 4;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      vst[r] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs_g[r], wo0, so, 0));
+      if (r > 0) vst[R + r - 1] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs_v[r - 1], wo0, so, 0));
+    }
+  };
+  // image offsets in floats: the writer's row 4 rq, frame 8 wg + fm; the reader's row n, slots 2h, 2h + 1
+  const int iwo = 4 * rq * 16 + 4 * ((2 * wg + (fm >> 2)) ^ (rq & 3)) + (fm & 3);
+  const int iro = n * 16 + 4 * ((2 * h) ^ ((n >> 2) & 3));
+  auto img_store = [&](float* im, int v) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) im[v * (D * 16) + iwo + c * 16] = vst[v][c];
+  };
+  auto img_read = [&](const float* im, f2 (&nx)[NV][4]) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const f4 a = ld4(im + v * (D * 16) + iro), b = ld4(im + v * (D * 16) + (iro ^ 4));
+      nx[v][0] = f2{a[0], a[1]}, nx[v][1] = f2{a[2], a[3]}, nx[v][2] = f2{b[0], b[1]}, nx[v][3] = f2{b[2], b[3]};
+    }
+  };
 
   f16v acc[CAP];
   float gb[CAP];
@@ -1770,27 +1821,25 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
     gb[k] = 0.f;
     acc[k] = f16v{};
   }
+  float* const imw = vimg + wv * IMG;   // VW 2: the image of the wave's j, buffer 0
   if (ft0 < ft1) {
     stage_load(ft0);
-    vec_load(nxa, ft0);
+    if constexpr (VW == 0) vec_load(nxa, ft0);
+    else img_load(ft0);
     stage_store(0);
     if (ft0 + 1 < ft1) stage_load(ft0 + 1);
+    if constexpr (VW == 2) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) img_store(imw, v);
+      img_load(min(ft0 + 1, ft1 - 1));
+    }
   }
   const int xoff = CG * 4 + (n * 16 + ((h ^ ((n >> 3) & 1)) * 8)) * 2;
   const float s0 = c0 * sg;
-  auto tile = [&](auto bufc, const f2 (&cur)[R + RV][4], f2 (&nxt)[R + RV][4], int ft) {
-    constexpr int buf = decltype(bufc)::value;
-    f2 g0[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) g0[v] = cur[0][v] * s0;
-    __syncthreads();   // tile ft staged in buf; buf ^ 1 (tile ft - 1) is free
-    if (ft + 1 < ft1) {
-      stage_store(buf ^ 1);
-      if (ft + 2 < ft1) stage_load(ft + 2);
-    }
-    // unconditional (the last tile reloads itself): no branch around the loads
-    vec_load(nxt, ft + 1 < ft1 ? ft + 1 : ft);
-    const unsigned char* sb = stg[buf];
+  // the wave's CAP capsules of the tile staged in buf, from the lane's vectors cur; VW 2
+  // with img_next: the wave's part of the next tile's image goes out behind the capsules
+  auto caps = [&](int buf, const f2 (&g0)[4], const f2 (&cur)[NV][4], bool img_next) {
+    const unsigned char* sb = stg[buf] + k0 * PCB;
 #pragma unroll
     for (int k = 0; k < CAP; ++k) {
       const unsigned char* ck = sb + k * PCB;
@@ -1820,14 +1869,58 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
       acc[k] = mfma32h(xh, bh, acc[k]);
       acc[k] = mfma32h(xh, bl, acc[k]);
       acc[k] = mfma32h(xl, bh, acc[k]);
+      if constexpr (VW == 2) {
+        // vectors v with v CAP / NV = k: all at the tile's start or end, the eight waves'
+        // stores came in one burst with nothing to hide them (measured)
+        if (img_next) {
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+            if (v * CAP / NV == k) img_store(imw + (buf ^ 1) * (4 * IMG), v);
+        }
+      }
     }
+  };
+  auto tile = [&](auto bufc, const f2 (&cur)[NV][4], f2 (&nxt)[NV][4], int ft) {
+    constexpr int buf = decltype(bufc)::value;
+    f2 g0[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) g0[v] = cur[0][v] * s0;
+    __syncthreads();   // tile ft staged in buf; buf ^ 1 (tile ft - 1) is free
+    if (ft + 1 < ft1) {
+      stage_store(buf ^ 1);
+      if (ft + 2 < ft1) stage_load(ft + 2);
+    }
+    // unconditional (the last tile reloads itself): no branch around the loads
+    vec_load(nxt, ft + 1 < ft1 ? ft + 1 : ft);
+    caps(buf, g0, cur, false);
+  };
+  // VW 2: the vectors run as the staged planes, one tile further ahead: after the barrier
+  // the wave reads tile ft's image; tile ft + 1's half image (loaded during tile ft - 1)
+  // goes to the other buffer between the capsules, then tile ft + 2's loads are issued
+  auto tile_img = [&](auto bufc, int ft) {
+    constexpr int buf = decltype(bufc)::value;
+    f2 cur[NV][4], g0[4];
+    __syncthreads();   // tile ft and its image staged in buf; buf ^ 1 (tile ft - 1) is free
+    img_read(imw + buf * (4 * IMG), cur);
+    if (ft + 1 < ft1) {
+      stage_store(buf ^ 1);
+      if (ft + 2 < ft1) stage_load(ft + 2);
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) g0[v] = cur[0][v] * s0;
+    caps(buf, g0, cur, ft + 1 < ft1);
+    // behind the capsules (their stores read vst); unconditional, the last tile reloads itself
+    __builtin_amdgcn_sched_barrier(0);
+    img_load(min(ft + 2, ft1 - 1));
   };
   using S0 = std::integral_constant<int, 0>;
   using S1 = std::integral_constant<int, 1>;
   for (int ft = ft0; ft < ft1; ft += 2) {
-    tile(S0{}, nxa, nxb, ft);
+    if constexpr (VW == 0) tile(S0{}, nxa, nxb, ft);
+    else tile_img(S0{}, ft);
     if (ft + 1 >= ft1) break;
-    tile(S1{}, nxb, nxa, ft + 1);
+    if constexpr (VW == 0) tile(S1{}, nxb, nxa, ft + 1);
+    else tile_img(S1{}, ft + 1);
   }
   float* gw = gwp + (size_t)s * pstride;
   float* gbo = gbp + (size_t)s * pstride;
@@ -1837,8 +1930,8 @@ __global__ __launch_bounds__(256, 2) void route_gw16s_kernel(
     const float a = gb[k];
     float pa, pb;
     xpair32(a, pa, pb);
-    if (k >= ncap || !wave_on) continue;
-    const int i = i0 + k;
+    if (k0 + k >= ncap || !wave_on) continue;
+    const int i = i0 + k0 + k;
     if (h == 0) gbo[(size_t)i * JD + row] = (pa + pb) * ug;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -2227,11 +2320,15 @@ int launch_gw2(const DrPlan& pl, const float* xT, const float* saved, const floa
   const int grid = p.n_rt * p.n_cc * p.S;
   if constexpr (D == 32) {
     if (pl.gw == GwPass::kGw16s) {   // 2 or 3 iterations
-      const int grid16 = SRF_GW16S_XCD ? (grid + 7) / 8 * 8 : grid;   // the kernel's XCD-aware task order
+      // VW 2: a workgroup of 8 waves takes two adjacent capsule groups of the plan (the
+      // last one alone where n_cc is odd); the plan, its splits and slabs are as for 4 waves
+      constexpr int VW = SRF_GW16S_LDSVEC, NG = VW == 2 ? 2 : 1;
+      const int tasks = p.n_rt * ((p.n_cc + NG - 1) / NG) * p.S;
+      const int grid16 = SRF_GW16S_XCD ? (tasks + 7) / 8 * 8 : tasks;   // the kernel's XCD-aware task order
       const _Float16* x16 = reinterpret_cast<const _Float16*>(xT);
-      hipLaunchKernelGGL((g.iters == 2 ? route_gw16s_kernel<2, kGw16Cap> : route_gw16s_kernel<3, kGw16Cap>), dim3(grid16),
-                         dim3(256), 0, st, x16, hdr, gumax, saved, gs, cst, glst, g.F(), Fp, g.in_n(), g.J, g.mask_first,
-                         JP, p.n_rt, p.S, p.ft_per, gwp, gbp, p.pstride);
+      hipLaunchKernelGGL((g.iters == 2 ? route_gw16s_kernel<2, kGw16Cap, VW> : route_gw16s_kernel<3, kGw16Cap, VW>),
+                         dim3(grid16), dim3(256 * NG), 0, st, x16, hdr, gumax, saved, gs, cst, glst, g.F(), Fp, g.in_n(),
+                         g.J, g.mask_first, JP, p.n_rt, p.S, p.ft_per, gwp, gbp, p.pstride);
       SRF_LAUNCH_CHECK("route_gw16s");
       return SRF_OK;
     }
