@@ -67,6 +67,14 @@ int srf_route_dr_fwd(const float* emb, const float* W, const float* bias, int B,
  * couplings: the plain entry points' behaviour (forward stores nothing, backward
  * recomputes).  Inference passes NULL. */
 size_t srf_route_dr_coupling_floats(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters);
+/* Where a training forward (couplings != NULL) leaves its prepared operands inside the
+ * coupling storage; launches nothing.  out[SRF_DR_LAYOUT_N]: float offset and byte length
+ * of Ws (0, 1), bs (2, 3), xs (4, 5), hdr (6, 7), WT (8, 9), xT (10, 11); JDp (12),
+ * xplane (13), Fp (14); whether WT (15) / xT (16) hold the split-fp16 formats (1) or fp32
+ * (0).  SRF_EUNSUPPORTED for a shape without coupling storage. */
+#define SRF_DR_LAYOUT_N 17
+int srf_route_dr_operand_layout(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters,
+                                long long* out);
 int srf_route_dr_fwd_ex(const float* emb, const float* W, const float* bias, int B, int T, int N, int din, int lpad,
                         int rpad, int J, int dout, int iters, int mask_first, int n_chunks, float* v_out,
                         float* saved, float* couplings, void* workspace, size_t workspace_bytes, void* stream);

@@ -61,6 +61,7 @@ _SIGNATURES = {
     'srf_route_dr_bwd_data': (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp, _vp, _vp, _c_size, _vp]),
     'srf_route_dr_bwd_weights': (_c_int, [_vp] + [_c_int] * 11 + [_vp, _vp, _vp, _c_size, _vp]),
     'srf_route_dr_coupling_floats': (_c_size, [_c_int] * 9),
+    'srf_route_dr_operand_layout': (_c_int, [_c_int] * 9 + [_vp]),   # out: long long[17]
     'srf_route_dr_fwd_ex': (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp, _vp, _vp, _c_size, _vp]),
     'srf_route_dr_bwd_ex': (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp] * 7 + [_c_size, _vp]),
     'srf_route_dr_bwd_data_ex': (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp] * 5 + [_c_size, _vp]),

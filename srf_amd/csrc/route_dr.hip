@@ -2790,6 +2790,41 @@ size_t srf_route_dr_coupling_floats(int B, int T, int N, int din, int lpad, int 
   return p.can_store ? p.cpl.total : 0;
 }
 
+int srf_route_dr_operand_layout(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters,
+                                long long* out) {
+  SRF_REQUIRE(out != nullptr, "operand_layout: null argument");
+  DrPlan p;
+  const DrGeom g{B, T, N, din, lpad, rpad, J, dout, iters, 0};
+  if (const int rc = check_geom(g)) return rc;
+  resolve(p, g, 0, true);
+  if (!p.couplings) {
+    srf::set_error("operand_layout: no coupling storage for this shape");
+    return SRF_EUNSUPPORTED;
+  }
+  const srf::Fwd32Shape& s = p.p32;
+  const size_t in_n = g.in_n(), Fp = padded_frames(g);
+  const size_t pl = p.cpl.planes;
+  const size_t v[SRF_DR_LAYOUT_N] = {pl,
+                                     2 * in_n * s.JDp * g.din * 2,
+                                     pl + s.ws_w / 4,
+                                     in_n * s.JDp * 8,
+                                     pl + (s.ws_w + s.ws_b) / 4,
+                                     2 * s.xplane * 2,
+                                     pl + (s.ws_w + s.ws_b + s.ws_x) / 4,
+                                     3 * sizeof(float),
+                                     p.cpl.WT,
+                                     in_n * g.din * ((size_t)g.NT() * 16) * 4,
+                                     p.cpl.xT,
+                                     in_n * g.din * Fp * 4,
+                                     (size_t)s.JDp,
+                                     s.xplane,
+                                     Fp,
+                                     p.gx == GxPass::kStored16 ? 1u : 0u,
+                                     p.gw == GwPass::kGw16s ? 1u : 0u};
+  for (int k = 0; k < SRF_DR_LAYOUT_N; ++k) out[k] = (long long)v[k];
+  return SRF_OK;
+}
+
 int srf_route_dr_fwd(const float* emb, const float* W, const float* bias, int B, int T, int N, int din, int lpad,
                      int rpad, int J, int dout, int iters, int mask_first, int n_chunks, float* v_out, float* saved,
                      void* workspace, size_t workspace_bytes, void* stream) {

@@ -8,7 +8,7 @@
 //
 // Pose product.  u = W x + b is formed on v_mfma_f32_32x32x16_f16 from 2-term fp16
 // splits of power-of-two scaled operands: W' = 2^aw W and x' = 2^bx x with
-// max|W'|, max|x'| < 2^14 (absmax_kernel + prep32_kernel, one global exponent per
+// max|W'|, max|x'| < 2^14 (absmax_kernel + prep32_onepass_kernel / prep32_kernel, one global exponent per
 // operand and forward), a' = a1 + a2 (a1 = f16(a'), a2 = f16(a' - a1)), keeping
 //     W'x' ~ W1x1 + W1x2 + W2x1                          (dropped W2x2 <= 2^-22 |W'x'|)
 // and the bias 2^(aw+bx) b through one bf16 MFMA (3-term bf16 split, exact to 2^-24)
@@ -58,6 +58,13 @@
 // the r >= 1 passes (an explicit plan argument still does).
 #ifndef SRF_DR_BAL_AUTO
 #define SRF_DR_BAL_AUTO 1
+#endif
+
+// SRF_PREP32_ONEPASS (A/B builds only): 1 = the din-32 operand preparation reads and splits
+// each operand once (prep32_onepass_kernel) behind a 1024-thread absmax; 0 = round 4's
+// prep32_kernel and 256-thread absmax for every shape.
+#ifndef SRF_PREP32_ONEPASS
+#define SRF_PREP32_ONEPASS 1
 #endif
 
 namespace {
@@ -111,9 +118,16 @@ __device__ __forceinline__ void split8h(const float* __restrict__ src, bool ok, 
 
 // Block maxima of |W| (blockIdx.y = 0) and |emb| (blockIdx.y = 1) -> part[y][blockIdx.x]
 // (kAbsBlocks per operand); prep32_kernel reduces them to the split exponents.
+// One-pass builds run 16 waves per block and four independent 16-byte loads per thread and
+// trip: at C4 (1.3 M / 2.9 M floats) a thread then needs one or two round trips where the
+// 4-wave blocks took 10 to 22, one after the other (the launch was 10 us of latency).
 constexpr int kAbsBlocks = 128;
-__global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ a, size_t na,
-                                                     const float* __restrict__ b, size_t nb, float* part) {
+constexpr int kAbsThreads = SRF_PREP32_ONEPASS ? 1024 : 256;
+__device__ __forceinline__ float absmax4(const f4& v) {
+  return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+}
+__global__ __launch_bounds__(kAbsThreads) void absmax_kernel(const float* __restrict__ a, size_t na,
+                                                             const float* __restrict__ b, size_t nb, float* part) {
   const float* p = blockIdx.y ? b : a;
   const size_t n = blockIdx.y ? nb : na;
   float m = 0.f;
@@ -121,6 +135,13 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ a
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if ((reinterpret_cast<uintptr_t>(p) & 15) == 0) {
     const size_t n4 = n / 4;
+    if (SRF_PREP32_ONEPASS) {
+      for (; i + 3 * stride < n4; i += 4 * stride) {
+        const f4* q = reinterpret_cast<const f4*>(p) + i;
+        const f4 v0 = q[0], v1 = q[stride], v2 = q[2 * stride], v3 = q[3 * stride];
+        m = fmaxf(m, fmaxf(fmaxf(absmax4(v0), absmax4(v1)), fmaxf(absmax4(v2), absmax4(v3))));
+      }
+    }
     for (; i < n4; i += stride) {
       const f4 v = reinterpret_cast<const f4*>(p)[i];
       m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
@@ -130,10 +151,14 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ a
   for (; i < n; i += stride) m = fmaxf(m, fabsf(p[i]));
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  __shared__ float wm[4];
+  __shared__ float wm[kAbsThreads / 64];
   if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
   __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.y * kAbsBlocks + blockIdx.x] = fmaxf(fmaxf(wm[0], wm[1]), fmaxf(wm[2], wm[3]));
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 1; k < kAbsThreads / 64; ++k) m = fmaxf(m, wm[k]);
+    part[blockIdx.y * kAbsBlocks + blockIdx.x] = m;
+  }
 }
 
 // One launch prepares every operand of a forward (thread ranges in this order):
@@ -159,9 +184,239 @@ struct PrepArgs {
   size_t xplane;
   size_t n_a, n_b, n_c, n_d, n_e;   // thread counts of the first five ranges
   size_t n_f, xt_block0;             // xT: 64-frame tiles, one block each from block xt_block0 on
+  // prep32_onepass_kernel: blocks [0, n_xblk) are x tiles, the next n_wblk W row groups
+  // (w_bpc per input capsule), the rest the n_b + n_c threads of the bias ranges
+  int rpad, n_xblk, n_wblk, w_bpc;
 };
 
 constexpr int kXtTile = 64;   // frames per xT tile of prep32_kernel
+
+// bs row idx = (i, row) of the bias range
+__device__ __forceinline__ void prep_bs(const PrepArgs& P, size_t idx, int aw, int bx) {
+  const int row = idx % P.JDp;
+  const size_t i = idx / P.JDp;
+  const float b = row < P.JD ? P.bias[i * P.JD + row] * exp2i(aw + bx) : 0.f;
+  __bf16 b1, b2, b3;
+  split3(b, b1, b2, b3);
+  bf4 v = {b1, b2, b3, (__bf16)0.f};
+  *reinterpret_cast<bf4*>(P.bs + idx * 4) = v;
+}
+
+// bsum element idx = (i-chunk c, row)
+__device__ __forceinline__ void prep_bsum(const PrepArgs& P, size_t idx) {
+  const int c = idx / P.JD, row = idx - (size_t)c * P.JD;
+  const int i0 = c * P.chunk_len, i1 = min(P.in_n, i0 + P.chunk_len);
+  float acc = 0.f;
+  // loads in batches of 8 (one round trip each), summed in capsule order
+  for (int i = i0; i < i1; i += 8) {
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = i + k < i1 ? P.bias[(size_t)(i + k) * P.JD + row] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc += v[k];
+  }
+  P.bsum[idx] = acc;
+}
+
+// ---- one-pass preparation, din 32 (SRF_PREP32_ONEPASS): every operand is read and split
+// once.  The bytes written are prep32_kernel's.
+//
+// x tile (blocks [0, n_xblk), block = 64-frame tile * N + capsule n): the tile's emb rows
+// and their window halo (frames f0 - lpad .. f0 + 63 + rpad, 128 bytes each) are read once
+// with 16-byte loads, scaled and split once, and kept in LDS as one word (hi | lo << 16)
+// per (e, row), e-major with an odd row stride.  The xs rows are stored from the
+// registers; wave kb then writes the 16-frame block kb of xT16 [i][f / 16][hi | lo][e][16]
+// for every window position w (capsule i = w*N + n): lane (e, 8-frame half) reads its 8
+// consecutive rows kb*16 + 8 hf + w + q of column e (bank e * 17 mod 32: no conflict) and
+// stores 16 bytes per plane, 1 KiB contiguous per wave and plane.  A frame past F, or whose
+// window row t + w - lpad leaves [0, T) of its own utterance, is zero: t comes from one
+// division per frame of the tile (tt), nothing per element.
+// The split exponent is reduced by each wave for itself (two loads per lane of the
+// 2 x kAbsBlocks block maxima and a shuffle tree, no barrier) after its operand loads are
+// issued.
+constexpr int kXHaloMax = 16;                        // lpad + rpad the LDS image holds
+constexpr int kXImgStride = kXtTile + kXHaloMax + 1;   // words per e (odd)
+
+__device__ __forceinline__ int wave_split_exp(const float* __restrict__ part, int y) {
+  const int l = threadIdx.x & 63;
+  float m = fmaxf(part[y * kAbsBlocks + l], part[y * kAbsBlocks + 64 + l]);
+  static_assert(kAbsBlocks == 128, "two block maxima per lane");
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  return split_exp(m);
+}
+
+// 4 scaled floats -> 4 (hi | lo << 16) words
+__device__ __forceinline__ void split4w(const f4& v, float s, uint32_t (&w)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    _Float16 a1, a2;
+    split2h(v[j] * s, a1, a2);
+    w[j] = (uint32_t)__builtin_bit_cast(uint16_t, a1) | ((uint32_t)__builtin_bit_cast(uint16_t, a2) << 16);
+  }
+}
+// the hi (sel = 0) or lo (sel = 1) halves of two words
+__device__ __forceinline__ uint32_t pack_hi(uint32_t a, uint32_t b) { return (a & 0xffffu) | (b << 16); }
+__device__ __forceinline__ uint32_t pack_lo(uint32_t a, uint32_t b) { return (a >> 16) | (b & 0xffff0000u); }
+
+typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+
+// LDS of a prep32_onepass_kernel block (words): the x image and its frame times, or four
+// wave-private W tiles of 64 rows (stride kWTileStride: 16-byte rows)
+constexpr int kWTileStride = 36;
+constexpr int kPrepLdsWords = 4 * 64 * kWTileStride;
+static_assert(32 * kXImgStride + kXtTile <= kPrepLdsWords && (32 * kXImgStride) % 4 == 0, "x image + tt fit");
+
+__device__ __forceinline__ void prep_x_tile(const PrepArgs& P, int blk, uint32_t* lds) {
+  uint32_t* const img = lds;
+  int* const tt = reinterpret_cast<int*>(lds + 32 * kXImgStride);
+  const int tid = threadIdx.x;
+  const int tile = blk / P.N, n = blk - tile * P.N;
+  const int f0 = tile * kXtTile;
+  const int nrow = kXtTile + P.lpad + P.rpad;   // image rows: frame f0 - lpad + r
+  constexpr int kIt = (kXtTile + kXHaloMax) * 8 / 256 + ((kXtTile + kXHaloMax) * 8 % 256 ? 1 : 0);
+  f4 v[kIt];
+#pragma unroll
+  for (int it = 0; it < kIt; ++it) {
+    const int k = tid + it * 256, r = k >> 3, e4 = k & 7;
+    const int fr = f0 - P.lpad + r;
+    v[it] = f4{0.f, 0.f, 0.f, 0.f};
+    if (r < nrow && fr >= 0 && fr < P.F)
+      v[it] = *reinterpret_cast<const f4*>(P.emb + ((size_t)fr * P.N + n) * 32 + 4 * e4);
+  }
+  if (tid < kXtTile) {
+    const int f = f0 + tid;
+    tt[tid] = f < P.F ? f - (f / P.T) * P.T : -(1 << 24);
+  }
+  if (blk == 0 && tid < 8) {   // the zero row after each plane (32 halves)
+    const h8 z = {};
+    *reinterpret_cast<h8*>(P.xs + (size_t)(tid >> 2) * P.xplane + (P.xplane - 32) + (tid & 3) * 8) = z;
+  }
+  const float sc = exp2i(wave_split_exp(P.part, 1));
+#pragma unroll
+  for (int it = 0; it < kIt; ++it) {
+    const int k = tid + it * 256, r = k >> 3, e4 = k & 7;
+    const int fr = f0 - P.lpad + r;
+    if (r >= nrow) continue;
+    uint32_t w[4];
+    split4w(v[it], sc, w);
+    if (P.xT) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) img[(4 * e4 + j) * kXImgStride + r] = w[j];
+    }
+    if (r >= P.lpad && r < P.lpad + kXtTile && fr < P.F) {
+      _Float16* d = P.xs + ((size_t)n * P.F + fr) * 32 + 4 * e4;
+      *reinterpret_cast<u2v*>(d) = u2v{pack_hi(w[0], w[1]), pack_hi(w[2], w[3])};
+      *reinterpret_cast<u2v*>(d + P.xplane) = u2v{pack_lo(w[0], w[1]), pack_lo(w[2], w[3])};
+    }
+  }
+  if (!P.xT) return;
+  __syncthreads();
+  const int e = tid & 31, hf = (tid >> 5) & 1, kb = tid >> 6;
+  const int fb = f0 + kb * 16;
+  if (fb >= P.Fp) return;
+  int t8[8];
+  {
+    const u4v a = *reinterpret_cast<const u4v*>(&tt[kb * 16 + hf * 8]);
+    const u4v b = *reinterpret_cast<const u4v*>(&tt[kb * 16 + hf * 8 + 4]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) t8[q] = (int)a[q] - P.lpad, t8[4 + q] = (int)b[q] - P.lpad;
+  }
+  _Float16* x16 = reinterpret_cast<_Float16*>(P.xT);
+  const uint32_t* col = img + e * kXImgStride + kb * 16 + hf * 8;
+  const int nwin = P.lpad + P.rpad + 1;
+  for (int w = 0; w < nwin; ++w) {
+    uint32_t c[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) c[q] = (uint32_t)(t8[q] + w) < (uint32_t)P.T ? col[w + q] : 0u;
+    const size_t i = (size_t)w * P.N + n;
+    const size_t base = ((i * (P.Fp / 16) + fb / 16) * 2 * 32 + e) * 16 + hf * 8;
+    *reinterpret_cast<u4v*>(x16 + base) =
+        u4v{pack_hi(c[0], c[1]), pack_hi(c[2], c[3]), pack_hi(c[4], c[5]), pack_hi(c[6], c[7])};
+    *reinterpret_cast<u4v*>(x16 + base + 32 * 16) =
+        u4v{pack_lo(c[0], c[1]), pack_lo(c[2], c[3]), pack_lo(c[4], c[5]), pack_lo(c[6], c[7])};
+  }
+}
+
+// W rows (blocks of 256 rows of one input capsule i, 64 per wave).  Lane (g, e4) reads the
+// 8 rows of row group g (rows 8h .. 8h + 7 of a 16-row tile t) by 4 columns with 8
+// independent 16-byte loads, splits them once and stores the (hi | lo << 16) words in the
+// wave's LDS tile [64 rows][32 columns] (16-byte stores, conflict-free).  The tile is then
+// written out twice, 1 KiB contiguous per wave, plane and store: the Ws rows (lane = row of
+// 16, 8 columns) and, for a training forward, the gx pass's [i][t][h][e][8] planes (lane =
+// column e of a row group: its 8 rows, 4-byte reads at consecutive banks).  Rows past JD
+// are zero.
+__device__ __forceinline__ void prep_w_rows(const PrepArgs& P, int blk, uint32_t* lds) {
+  const int i = blk / P.w_bpc, rb = blk - i * P.w_bpc;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int e4 = lane & 7, g = lane >> 3;
+  const int rw0 = rb * 256 + wv * 64;    // the wave's rows; JDp is a multiple of 64
+  const bool active = rw0 < P.JDp;
+  uint32_t* const t = lds + wv * 64 * kWTileStride;
+  f4 v[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int row = rw0 + g * 8 + k;
+    v[k] = f4{0.f, 0.f, 0.f, 0.f};
+    if (row < P.JD) v[k] = *reinterpret_cast<const f4*>(P.W + ((size_t)i * P.JD + row) * 32 + 4 * e4);
+  }
+  const float s = exp2i(wave_split_exp(P.part, 0));
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    uint32_t w[4];
+    split4w(v[k], s, w);
+    *reinterpret_cast<u4v*>(t + (g * 8 + k) * kWTileStride + 4 * e4) = u4v{w[0], w[1], w[2], w[3]};
+  }
+  __syncthreads();
+  if (!active) return;
+  const size_t nw = (size_t)P.in_n * P.JDp * 32;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int rl = it * 16 + (lane >> 2), c8 = (lane & 3) * 8;
+    const u4v a = *reinterpret_cast<const u4v*>(t + rl * kWTileStride + c8);
+    const u4v b = *reinterpret_cast<const u4v*>(t + rl * kWTileStride + c8 + 4);
+    _Float16* d = P.Ws + ((size_t)i * P.JDp + rw0 + rl) * 32 + c8;
+    *reinterpret_cast<u4v*>(d) = u4v{pack_hi(a[0], a[1]), pack_hi(a[2], a[3]), pack_hi(b[0], b[1]), pack_hi(b[2], b[3])};
+    *reinterpret_cast<u4v*>(d + nw) =
+        u4v{pack_lo(a[0], a[1]), pack_lo(a[2], a[3]), pack_lo(b[0], b[1]), pack_lo(b[2], b[3])};
+  }
+  if (P.WT == nullptr) return;
+  const int nt16 = (P.JD + 15) / 16;
+  const int e = lane & 31;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int g2 = it * 2 + (lane >> 5);
+    const int r0 = rw0 + g2 * 8;
+    if (r0 >= nt16 * 16) continue;
+    uint32_t c[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) c[q] = t[(g2 * 8 + q) * kWTileStride + e];
+    _Float16* d = reinterpret_cast<_Float16*>(P.WT) + (((size_t)i * nt16 * 2 + r0 / 8) * 32 + e) * 8;
+    *reinterpret_cast<u4v*>(d) = u4v{pack_hi(c[0], c[1]), pack_hi(c[2], c[3]), pack_hi(c[4], c[5]), pack_hi(c[6], c[7])};
+    *reinterpret_cast<u4v*>(d + P.n_e * 8) =
+        u4v{pack_lo(c[0], c[1]), pack_lo(c[2], c[3]), pack_lo(c[4], c[5]), pack_lo(c[6], c[7])};
+  }
+}
+
+__global__ __launch_bounds__(256) void prep32_onepass_kernel(PrepArgs P) {
+  __shared__ __attribute__((aligned(16))) uint32_t lds[kPrepLdsWords];
+  int blk = blockIdx.x;
+  if (blk < P.n_xblk) return prep_x_tile(P, blk, lds);
+  blk -= P.n_xblk;
+  if (blk < P.n_wblk) return prep_w_rows(P, blk, lds);
+  blk -= P.n_wblk;
+  const int aw = wave_split_exp(P.part, 0), bx = wave_split_exp(P.part, 1);
+  if (blk == 0 && threadIdx.x == 0) {
+    P.hdr[0] = exp2i(-(aw + bx));
+    P.hdr[1] = (float)aw;
+    P.hdr[2] = (float)bx;
+  }
+  size_t idx = (size_t)blk * blockDim.x + threadIdx.x;
+  if (idx < P.n_b) return prep_bs(P, idx, aw, bx);
+  idx -= P.n_b;
+  if (idx < P.n_c) prep_bsum(P, idx);
+}
 
 __global__ __launch_bounds__(256) void prep32_kernel(PrepArgs P) {
   if (P.n_f && blockIdx.x >= P.xt_block0) {
@@ -259,29 +514,12 @@ __global__ __launch_bounds__(256) void prep32_kernel(PrepArgs P) {
   }
   idx -= P.n_a;
   if (idx < P.n_b) {
-    const int row = idx % P.JDp;
-    const size_t i = idx / P.JDp;
-    const float b = row < P.JD ? P.bias[i * P.JD + row] * exp2i(aw + bx) : 0.f;
-    __bf16 b1, b2, b3;
-    split3(b, b1, b2, b3);
-    bf4 v = {b1, b2, b3, (__bf16)0.f};
-    *reinterpret_cast<bf4*>(P.bs + idx * 4) = v;
+    prep_bs(P, idx, aw, bx);
     return;
   }
   idx -= P.n_b;
   if (idx < P.n_c) {
-    const int c = idx / P.JD, row = idx - (size_t)c * P.JD;
-    const int i0 = c * P.chunk_len, i1 = min(P.in_n, i0 + P.chunk_len);
-    float acc = 0.f;
-    // loads in batches of 8 (one round trip each), summed in capsule order
-    for (int i = i0; i < i1; i += 8) {
-      float v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = i + k < i1 ? P.bias[(size_t)(i + k) * P.JD + row] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) acc += v[k];
-    }
-    P.bsum[idx] = acc;
+    prep_bsum(P, idx);
     return;
   }
   idx -= P.n_c;
@@ -2334,8 +2572,8 @@ int fwd32_prepare(const Fwd32Plan& p, const DrGeom& g, const float* emb, const f
   char* base = static_cast<char*>(planes);
   float* hdr = reinterpret_cast<float*>(base + p.ws_w + p.ws_b + p.ws_x);
   const int din = g.din;
-  hipLaunchKernelGGL(absmax_kernel, dim3(kAbsBlocks, 2), dim3(256), 0, st, W, (size_t)g.in_n() * g.JD() * din, emb,
-                     (size_t)g.F() * g.N * din, hdr + 64);
+  hipLaunchKernelGGL(absmax_kernel, dim3(kAbsBlocks, 2), dim3(kAbsThreads), 0, st, W,
+                     (size_t)g.in_n() * g.JD() * din, emb, (size_t)g.F() * g.N * din, hdr + 64);
   SRF_LAUNCH_CHECK("absmax");
   PrepArgs P;
   P.W = W;
@@ -2370,6 +2608,23 @@ int fwd32_prepare(const Fwd32Plan& p, const DrGeom& g, const float* emb, const f
   SRF_REQUIRE(!xt16 || din == 32, "prep32: split x^T planes need din 32, got %d", din);
   P.xt16 = xt16 ? 1 : 0;
   P.n_e = WT ? (size_t)P.in_n * ((P.JD + 15) / 16) * (wt16 ? 2 : 4) * din : 0;
+  P.rpad = g.rpad;
+  P.n_xblk = P.n_wblk = P.w_bpc = 0;
+  P.n_f = P.xt_block0 = 0;
+  // din 32 with the split-fp16 backward operands (or none: eval, streaming): one pass per operand
+  if (SRF_PREP32_ONEPASS && din == 32 && (!WT || wt16) && (!xT || xt16) && P.JD % 8 == 0 &&
+      g.lpad + g.rpad <= kXHaloMax) {
+    const size_t n_xblk = (size_t)((P.F + kXtTile - 1) / kXtTile) * P.N;
+    P.w_bpc = (P.JDp + 255) / 256;
+    const size_t n_wblk = (size_t)P.in_n * P.w_bpc;
+    const size_t n_blk = n_xblk + n_wblk + (P.n_b + P.n_c + 255) / 256;
+    SRF_REQUIRE(n_blk < (1ull << 31), "prep32: %zu blocks", n_blk);
+    P.n_xblk = (int)n_xblk;
+    P.n_wblk = (int)n_wblk;
+    hipLaunchKernelGGL(prep32_onepass_kernel, dim3((unsigned)n_blk), dim3(256), 0, st, P);
+    SRF_LAUNCH_CHECK("prep32_onepass");
+    return SRF_OK;
+  }
   SRF_REQUIRE(din <= 32, "prep32: xT tile holds din <= 32, got %d", din);
   P.n_f = xT ? (size_t)P.in_n * ((P.Fp + kXtTile - 1) / kXtTile) : 0;   // xT tiles (one block each)
   P.xt_block0 = (P.n_a + P.n_b + P.n_c + P.n_d + P.n_e + 255) / 256;
