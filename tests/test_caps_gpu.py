@@ -2,7 +2,19 @@
 dropout, output head) and of the CTC kernel, through the C ABI, against float64
 torch-autograd restatements (tests/torch_ref.py) with bit-identical dropout
 masks.  Tolerances: values |err| <= 1e-4 * (1 + |ref|); gradients
-|err| <= 1e-3 * max|ref| + 1e-6; CTC NLL within 1e-4 relative."""
+|err| <= 1e-3 * max|ref| + 1e-6; CTC NLL within 1e-4 relative.
+
+What the cases of this file reach (srf::colsum picks its kernel from the row count,
+reduce.hip; the other routes are tests/test_caps_rows_gpu.py's):
+  test_primary_caps       F = 33 frames, K = 1984: the MFMA projection forward, the
+                          float4 g_X kernel with 3 frame groups, the MFMA wgrad with
+                          fchunk = 1 (one batch, one live frame per chunk);
+                          colsum(wpart, 33 rows) and colsum(ppart, 64 rows): one pass of
+                          colsum_stage2 (rows <= 128)
+  test_capsnorm_and_head  F = 18 frames: the block kernels (n = 128, 1008) and the
+                          wave kernels (n = 256, 512, 1024; 5 partial rows); head
+                          backward on the block kernel; every column sum is one pass
+                          of colsum_stage2"""
 import numpy as np
 import pytest
 import torch
