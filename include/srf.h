@@ -586,6 +586,38 @@ int srf_ctc_beam_best(const void* state, size_t state_bytes, int B, int C, int b
  * 1 <= N <= beam_width and max_len >= 1. */
 int srf_ctc_beam_nbest(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int N,
                        int max_len, int* labels, int* count, float* log_prob, int* n_hyp, void* stream);
+/* srf_ctc_beam_lm_*: the same search with a language model fused into the beam (shallow
+ * fusion; srf_ctc_beam_search_lm in srf_data.h defines the result).  The model is a
+ * deterministic automaton over the classes in two device tables of n_states rows:
+ *   bonus [n_states][C] float32, finite: what extending a prefix in state s by class c adds
+ *     to its score (alpha * log p_lm(c | s) + beta; the blank's column is never read),
+ *   next [n_states][C] int32 in [0, n_states): the state after that extension;
+ * state 0 belongs to the empty prefix.  The one change to the search: the extension of a
+ * prefix in state s by class c is
+ *   pnb'(l + c) = ((c == last ? pb : tot) + lp[c]) + bonus[s][c]      (fp32, in this order),
+ * also where an entry folds in its parent's extension (with the parent's state); the blank
+ * and repeat steps add nothing.  The ranking score is log p_ctc(prefix) + the sum of the
+ * prefix's bonuses; keys, tie rule, selection and hashing are those of srf_ctc_beam_*.
+ *
+ * The state block has its own size (srf_ctc_beam_lm_state_bytes: two more beam arrays, the
+ * entry's state and its accumulated bonus) and is not interchangeable with the unfused
+ * one; reset, push_n, best and nbest take the arguments of their unfused namesakes.
+ * push_n also takes the tables and is refused for a null table, n_states < 1 or
+ * n_states * C >= 2^31; the same tables belong to every push between two resets.  The
+ * kernel clamps states to [0, n_states), so no table content makes it read outside the
+ * tables.  best / nbest: score is the ranking score, lm_score ([B], [B][N]) the
+ * accumulated bonus of that prefix (0 past n_hyp), their difference its CTC part. */
+size_t srf_ctc_beam_lm_state_bytes(int B, int C, int beam_width, int max_frames);
+int srf_ctc_beam_lm_reset(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                          int* frames_pushed, void* stream);
+int srf_ctc_beam_lm_push_n(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int blank,
+                           const float* logits, const int* n_valid, int n, const float* bonus, const int* next,
+                           int n_states, int* frames_pushed, void* stream);
+int srf_ctc_beam_lm_best(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                         int* labels, int* count, float* score, float* lm_score, void* stream);
+int srf_ctc_beam_lm_nbest(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int N,
+                          int max_len, int* labels, int* count, float* score, float* lm_score, int* n_hyp,
+                          void* stream);
 
 /* ---- MWER: expected error over an N-best list (tfsr/helper/train_helper.py
  * loss_ewerr) ----------------------------------------------------------------

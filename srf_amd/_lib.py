@@ -154,6 +154,12 @@ _SIGNATURES = {
     'srf_ctc_beam_push_n': (_c_int, [_vp, _c_size] + [_c_int] * 5 + [_vp, _vp, _c_int, ctypes.POINTER(_c_int), _vp]),
     'srf_ctc_beam_best': (_c_int, [_vp, _c_size] + [_c_int] * 4 + [_vp, _vp, _vp, _vp]),
     'srf_ctc_beam_nbest': (_c_int, [_vp, _c_size] + [_c_int] * 6 + [_vp, _vp, _vp, _vp, _vp]),
+    'srf_ctc_beam_lm_state_bytes': (_c_size, [_c_int] * 4),
+    'srf_ctc_beam_lm_reset': (_c_int, [_vp, _c_size] + [_c_int] * 4 + [ctypes.POINTER(_c_int), _vp]),
+    'srf_ctc_beam_lm_push_n': (_c_int, [_vp, _c_size] + [_c_int] * 5 + [_vp, _vp, _c_int, _vp, _vp, _c_int,
+                                                                       ctypes.POINTER(_c_int), _vp]),
+    'srf_ctc_beam_lm_best': (_c_int, [_vp, _c_size] + [_c_int] * 4 + [_vp, _vp, _vp, _vp, _vp]),
+    'srf_ctc_beam_lm_nbest': (_c_int, [_vp, _c_size] + [_c_int] * 6 + [_vp, _vp, _vp, _vp, _vp, _vp]),
     'srf_mwer_workspace': (_c_size, [_c_int] * 5),
     'srf_mwer_loss': (_c_int, [_vp] * 6 + [_c_int] * 6 + [ctypes.c_float] + [_vp] * 5 + [_c_size, _vp]),
     'srf_stream_advance_n': (_c_int, [ctypes.POINTER(StreamBuf), _c_int, _c_int, _vp]),

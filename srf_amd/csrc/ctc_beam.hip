@@ -31,6 +31,14 @@
 // are ranked by counting and placed in rank order, new prefixes taking trie nodes in that
 // order, so the state after a frame is a pure function of the state before it and the
 // frame, whatever the chunking.
+//
+// With a language model fused in (srf_ctc_beam_lm_*) every extension
+// also gets bonus[state of the prefix][class].  The push kernel is one template: without
+// tables it is the kernel above, instruction for instruction; with them every entry carries
+// its automaton state and accumulated bonus (two more beam arrays in the state block), and
+// a frame's candidate bonuses are copied global -> LDS while the per-slot step runs.
+#include <type_traits>
+
 #include "srf_common.h"
 #include "../../include/srf.h"
 
@@ -41,17 +49,21 @@ constexpr int kMaxW = SRF_CTC_BEAM_MAX_WIDTH;
 constexpr int kMaxC = SRF_CTC_BEAM_MAX_CLASSES;
 constexpr int kHeader = 4;   // state words per utterance before the beam: entries, trie nodes, frames, unused
 constexpr int kFields = 9;   // beam arrays: node, pb, pnb, last, len, hash (2 words), parent's hash (2 words)
+constexpr int kLmFields = kFields + 2;   // with a fused language model: its state, the accumulated bonus
+template <bool kLM>
+constexpr int kFieldsOf = kLM ? kLmFields : kFields;
 constexpr unsigned long long kRootHash = 0x243f6a8885a308d3ull;
 static_assert(kMaxW * kMaxC <= (1 << 14), "a candidate key takes 14 bits");
 constexpr int kPerLane = kMaxW * kMaxC / kThreads;   // candidates a lane looks at, at most
+static_assert(kPerLane % 8 == 0, "the fused kernel copies the bonuses in groups of eight keys per lane");
 static_assert(kThreads == 4 * kMaxW, "the ranking pass splits the survivors over four quarters of the workgroup");
 
 constexpr unsigned kKeyMax = (1u << 14) - 1;
 constexpr unsigned char kNoFold = 0xff;
 
 __host__ __device__ inline size_t trie_capacity(int W, int max_frames) { return 1 + (size_t)max_frames * W; }
-__host__ __device__ inline size_t state_words(int W, int max_frames) {
-  return kHeader + (size_t)kFields * W + 2 * trie_capacity(W, max_frames);
+__host__ __device__ inline size_t state_words(int W, int max_frames, int fields) {
+  return kHeader + (size_t)fields * W + 2 * trie_capacity(W, max_frames);
 }
 
 // hash of prefix + (c,) from the prefix's (the splitmix64 finaliser over hash ^ f(c))
@@ -83,7 +95,28 @@ __device__ __forceinline__ float unordered(unsigned u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
-struct alignas(16) Smem {
+// A fused language model: a deterministic automaton over the classes
+// as two device tables, bonus [S][C] (what extending a prefix in state s by class c adds to
+// its score) and next [S][C] (the state after it).  Both are functions of the prefix alone,
+// as its hash is, so merging and re-made parents stay consistent.
+struct LmTables {
+  const float* bonus;
+  const int* next;
+  int S;
+};
+struct NoLmBeam {};
+struct LmBeam {
+  // [key]: the candidate's bonus, this frame.  First in the workgroup's LDS (Smem's base
+  // class, the kernel's only shared variable): the global -> LDS copies that fill it take
+  // their LDS address from M0, and all of it lies below 64 KiB.
+  float cb[kMaxW * kMaxC];
+  int lmst[2][kMaxW];    // the entry's state, in [0, S)
+  float acc[2][kMaxW];   // the bonuses of its labels, added in label order
+};
+static_assert(sizeof(LmBeam::cb) <= (1 << 16), "the candidates' bonuses lie in the first 64 KiB of LDS");
+
+template <bool kLM>
+struct alignas(16) Smem : std::conditional_t<kLM, LmBeam, NoLmBeam> {
   float lp[kMaxC];
   // the beam, double-buffered over frames
   int node[2][kMaxW];
@@ -112,7 +145,23 @@ struct Cand {
 
 __device__ __forceinline__ int class_of(int j, int blank) { return j - 1 < blank ? j - 1 : j; }
 
-__device__ __forceinline__ Cand candidate(const Smem& s, int cur, int i, const FastDiv& divC, int C, int blank) {
+// Fused: where candidate i's bonus lies, bonus[state of its slot][its class].  Keys of
+// consecutive lanes are consecutive classes of one slot, so a wave reads runs of a row.  A
+// slot's own candidate (j = 0) has no class and reads its first extension's word, unused.
+// A key past the last candidate reads the last slot's row (no branch; its word is unused too).
+__device__ __forceinline__ int bonus_index(const Smem<true>& s, int cur, int i, const FastDiv& divC, int C,
+                                           int blank, int nb) {
+  const int k = (int)fdiv((unsigned)i, divC), j = max(i - k * C, 1);
+  return s.lmst[cur][min(k, nb - 1)] * C + class_of(j, blank);
+}
+
+__device__ __forceinline__ void glds4(const float* src, float* lds_dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds_dst, 4, 0, 0);
+}
+
+template <bool kLM>
+__device__ __forceinline__ Cand candidate(const Smem<kLM>& s, int cur, int i, const FastDiv& divC, int C, int blank) {
   const int k = (int)fdiv((unsigned)i, divC), j = i - k * C;
   Cand r{0u, 0, k};
   if (j == 0) {
@@ -128,7 +177,10 @@ __device__ __forceinline__ Cand candidate(const Smem& s, int cur, int i, const F
   const int c = class_of(j, blank);
   const float prev = c == s.last[cur][k] ? s.pb[cur][k] : s.tot[k];
   if (prev == neg_inf()) return r;
-  r.u = ordered(prev + s.lp[c]);
+  if constexpr (kLM)
+    r.u = ordered((prev + s.lp[c]) + s.cb[i]);
+  else
+    r.u = ordered(prev + s.lp[c]);
   r.ext = 1;
   return r;
 }
@@ -136,7 +188,8 @@ __device__ __forceinline__ Cand candidate(const Smem& s, int cur, int i, const F
 // Wave 0 after a histogram pass: the bin in which the need-th largest matching candidate
 // lies, how many lie in higher bins, and how many in that bin.  first: need is the beam
 // width capped by the number of candidates.
-__device__ __forceinline__ void pick_bin(Smem& s, const unsigned* h, int need, bool first, int W) {
+template <bool kLM>
+__device__ __forceinline__ void pick_bin(Smem<kLM>& s, const unsigned* h, int need, bool first, int W) {
   const int lane = threadIdx.x;
   const uint4 v = reinterpret_cast<const uint4*>(h)[lane];
   const int b[4] = {(int)v.x, (int)v.y, (int)v.z, (int)v.w};
@@ -165,19 +218,27 @@ __device__ __forceinline__ void pick_bin(Smem& s, const unsigned* h, int need, b
   }
 }
 
+__device__ __forceinline__ const LmTables& tables_of(const LmTables& lm) { return lm; }
+
+// Lm: nothing, and this is the search of section 12 with the arguments it always had, or
+// LmTables, and bonus[state][c] is added to every extension (section 17).
+template <class... Lm>
 __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __restrict__ state,
                                                                  const float* __restrict__ logits,
                                                                  const int* __restrict__ n_valid, int n, int C,
-                                                                 int blank, int W, int max_frames, FastDiv divC) {
-  __shared__ Smem s;
+                                                                 int blank, int W, int max_frames, FastDiv divC,
+                                                                 Lm... tables) {
+  constexpr bool kLM = sizeof...(Lm) == 1;
+  static_assert(sizeof...(Lm) <= 1, "at most one language model");
+  __shared__ Smem<kLM> s;
   const int b = blockIdx.x, t = threadIdx.x;
   const int nv = max(0, min(n_valid[b], n));
   if (nv == 0) return;
   const size_t cap = trie_capacity(W, max_frames);
-  unsigned* st = state + (size_t)b * state_words(W, max_frames);
+  unsigned* st = state + (size_t)b * state_words(W, max_frames, kFieldsOf<kLM>);
   int* hdr = reinterpret_cast<int*>(st);
   unsigned* beam = st + kHeader;
-  int* trie_parent = reinterpret_cast<int*>(beam + (size_t)kFields * W);
+  int* trie_parent = reinterpret_cast<int*>(beam + (size_t)kFieldsOf<kLM> * W);
   int* trie_label = trie_parent + cap;
   const float* x = logits + (size_t)b * n * C;
 
@@ -193,6 +254,11 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
     s.len[0][t] = (int)beam[4 * W + t];
     s.hash[0][t] = (unsigned long long)beam[6 * W + t] << 32 | beam[5 * W + t];
     s.phash[0][t] = (unsigned long long)beam[8 * W + t] << 32 | beam[7 * W + t];
+    if constexpr (kLM) {
+      // (clamped as last is: a block that was never reset does not index outside the tables)
+      s.lmst[0][t] = min(max((int)beam[9 * W + t], 0), tables_of(tables...).S - 1);
+      s.acc[0][t] = __uint_as_float(beam[10 * W + t]);
+    }
   }
   if (t < kMaxW) s.ps[t] = -1;
   for (int i = t; i < kMaxW * kMaxC / 4; i += kThreads) reinterpret_cast<unsigned*>(s.fold)[i] = 0xffffffffu;
@@ -206,6 +272,11 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
     if (t < C) xa = x[t];
     if (t + 64 < C) xb = x[t + 64];
   }
+
+  // Fused: a lane's candidates' bonuses.  They depend on the beam alone, not on the frame, so
+  // they are asked for at the start of a frame, all at once, and arrive from L2 while the
+  // parent match, the log-softmax and the per-slot step run; uc[m] holds the bonus until the
+  // candidate's ordered total takes its place.
 
   for (int f = 0; f < nv; ++f) {
     // ---- every entry's parent slot: the entry one label shorter whose hash is its parent's
@@ -237,6 +308,31 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
     }
     __syncthreads();
 
+    // Fused: every candidate's bonus, global -> LDS without passing through registers (the
+    // sweeps below leave none).  They depend on the beam alone and land while the per-slot
+    // step runs; the barrier after it waits for them.  Whole waves issue: the copy's LDS
+    // address is the wave's first lane's plus 4 bytes per lane.
+    if constexpr (kLM) {
+      const int ncand = nb * C;
+      // (the lane index made opaque: computed from t, the 32 slot and class indices would be
+      // kept in registers over the whole frame loop, and there are none left for them)
+      int lane = t;
+      asm volatile("" : "+v"(lane));
+      // Groups of eight without a branch inside: a group's eight state reads from LDS come
+      // first and its copies go out back to back; a key past the last candidate copies a
+      // word nobody uses.
+#pragma unroll
+      for (int g = 0; g < kPerLane; g += 8) {
+        if (g * kThreads >= ncand) break;
+        int at[8];   // (read before the group's first copy: a copy writes LDS, and no read moves across it)
+#pragma unroll
+        for (int m = 0; m < 8; ++m) at[m] = bonus_index(s, cur, (g + m) * kThreads + lane, divC, C, blank, nb);
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+          glds4(tables_of(tables...).bonus + at[m], &s.cb[(g + m) * kThreads + lane]);
+      }
+    }
+
     // ---- per beam slot: its own candidate, with its parent's extension folded in
     if (t < kMaxW) {
       s.rank[t] = 0;
@@ -246,6 +342,10 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
     if (t < nb) {
       const float pb = s.pb[cur][t], pnb = s.pnb[cur][t];
       const int last = s.last[cur][t], ps = s.ps[t];
+      float fold_bonus = 0.f;   // fused: of the parent's extension by last, from the parent's state
+      if constexpr (kLM) {
+        if (ps >= 0) fold_bonus = tables_of(tables...).bonus[s.lmst[cur][ps] * C + last];
+      }
       const float tot = log_sum_exp(pb, pnb);
       float npnb = last >= 0 ? pnb + s.lp[last] : neg_inf();
       int alias = t * C, fidx = -1;
@@ -253,7 +353,10 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
         const float ppb = s.pb[cur][ps];
         const float prev = last == s.last[cur][ps] ? ppb : log_sum_exp(ppb, s.pnb[cur][ps]);
         if (prev != neg_inf()) {
-          npnb = log_sum_exp(npnb, prev + s.lp[last]);
+          if constexpr (kLM)
+            npnb = log_sum_exp(npnb, (prev + s.lp[last]) + fold_bonus);
+          else
+            npnb = log_sum_exp(npnb, prev + s.lp[last]);
           fidx = ps * C + 1 + (last < blank ? last : last - 1);
           s.fold[fidx] = (unsigned char)t;
           alias = min(alias, fidx);
@@ -380,8 +483,19 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
         s.len[nxt][r] = s.len[cur][from];
         s.hash[nxt][r] = s.hash[cur][from];
         s.phash[nxt][r] = s.phash[cur][from];
+        if constexpr (kLM) {
+          s.lmst[nxt][r] = s.lmst[cur][from];
+          s.acc[nxt][r] = s.acc[cur][from];
+        }
       } else {
         const int c = class_of(j, blank);
+        if constexpr (kLM) {
+          // the only read of next: a survivor that is a new prefix.  (Clamped like a state
+          // from the block: a table that breaks its contract cannot lead outside the tables.)
+          const int at = s.lmst[cur][k] * C + c;
+          s.lmst[nxt][r] = min(max(tables_of(tables...).next[at], 0), tables_of(tables...).S - 1);
+          s.acc[nxt][r] = s.acc[cur][k] + tables_of(tables...).bonus[at];
+        }
         const size_t id = (size_t)n_nodes + s.extb[t];
         if (id < cap) {   // holds while the frames pushed stay within max_frames (checked on the host)
           trie_parent[id] = s.node[cur][k];
@@ -415,6 +529,10 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
     beam[6 * W + t] = (unsigned)(s.hash[cur][t] >> 32);
     beam[7 * W + t] = (unsigned)s.phash[cur][t];
     beam[8 * W + t] = (unsigned)(s.phash[cur][t] >> 32);
+    if constexpr (kLM) {
+      beam[9 * W + t] = (unsigned)s.lmst[cur][t];
+      beam[10 * W + t] = __float_as_uint(s.acc[cur][t]);
+    }
   }
   if (t == 0) {
     hdr[0] = nb;
@@ -423,12 +541,13 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
   }
 }
 
+template <bool kLM>
 __global__ __launch_bounds__(64) void ctc_beam_reset_kernel(unsigned* __restrict__ state, int W, int max_frames) {
   if (threadIdx.x != 0) return;
-  unsigned* st = state + (size_t)blockIdx.x * state_words(W, max_frames);
+  unsigned* st = state + (size_t)blockIdx.x * state_words(W, max_frames, kFieldsOf<kLM>);
   int* hdr = reinterpret_cast<int*>(st);
   unsigned* beam = st + kHeader;
-  int* trie_parent = reinterpret_cast<int*>(beam + (size_t)kFields * W);
+  int* trie_parent = reinterpret_cast<int*>(beam + (size_t)kFieldsOf<kLM> * W);
   hdr[0] = 1;
   hdr[1] = 1;
   hdr[2] = 0;
@@ -441,22 +560,29 @@ __global__ __launch_bounds__(64) void ctc_beam_reset_kernel(unsigned* __restrict
   beam[5 * W] = (unsigned)kRootHash;
   beam[6 * W] = (unsigned)(kRootHash >> 32);
   beam[7 * W] = beam[8 * W] = 0;              // no parent
+  if constexpr (kLM) {
+    beam[9 * W] = 0;                          // state 0 belongs to the empty prefix
+    beam[10 * W] = __float_as_uint(0.f);      // no bonus yet
+  }
   trie_parent[0] = -1;
   trie_parent[trie_capacity(W, max_frames)] = -1;   // label of the root
 }
 
 // One wave per utterance.  The first slot with the largest total (after a frame the beam
 // is in rank order, so slot 0); lane 0 walks the trie from its node to the root.
+// (fused: log_prob is the ranking score, lm_score the accumulated bonus of that entry)
+template <bool kLM>
 __global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __restrict__ state, int W, int max_frames,
                                                            int* __restrict__ labels, int* __restrict__ count,
-                                                           float* __restrict__ log_prob) {
+                                                           float* __restrict__ log_prob,
+                                                           float* __restrict__ lm_score) {
   if (threadIdx.x != 0) return;
   const int b = blockIdx.x;
   const size_t cap = trie_capacity(W, max_frames);
-  const unsigned* st = state + (size_t)b * state_words(W, max_frames);
+  const unsigned* st = state + (size_t)b * state_words(W, max_frames, kFieldsOf<kLM>);
   const int* hdr = reinterpret_cast<const int*>(st);
   const unsigned* beam = st + kHeader;
-  const int* trie_parent = reinterpret_cast<const int*>(beam + (size_t)kFields * W);
+  const int* trie_parent = reinterpret_cast<const int*>(beam + (size_t)kFieldsOf<kLM> * W);
   const int* trie_label = trie_parent + cap;
   const int nb = min(max(hdr[0], 1), W);
   int best = 0;
@@ -477,6 +603,7 @@ __global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __res
   }
   count[b] = len;
   log_prob[b] = best_tot;
+  if constexpr (kLM) lm_score[b] = __uint_as_float(beam[10 * W + best]);
 }
 
 // The N first beam entries of each utterance.  After a frame the beam lies in rank order
@@ -484,17 +611,19 @@ __global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __res
 // frame the root is the only entry.  The walk from a node to the root follows parent
 // pointers and is serial, so a lane walks one hypothesis: a wave holds 64 (utterance,
 // hypothesis) pairs, every lane on its own trie path.  Grid (B, ceil(N / 64)).
+// (Fused: lm_score [B][N] gets each entry's accumulated bonus, 0 past the beam's entries.)
+template <bool kLM>
 __global__ __launch_bounds__(64) void ctc_beam_nbest_kernel(const unsigned* __restrict__ state, int W, int max_frames,
                                                             int N, int max_len, int* __restrict__ labels,
                                                             int* __restrict__ count, float* __restrict__ log_prob,
-                                                            int* __restrict__ n_hyp) {
+                                                            float* __restrict__ lm_score, int* __restrict__ n_hyp) {
   const int b = blockIdx.x, i = blockIdx.y * 64 + threadIdx.x;
   if (i >= N) return;
   const size_t cap = trie_capacity(W, max_frames);
-  const unsigned* st = state + (size_t)b * state_words(W, max_frames);
+  const unsigned* st = state + (size_t)b * state_words(W, max_frames, kFieldsOf<kLM>);
   const int* hdr = reinterpret_cast<const int*>(st);
   const unsigned* beam = st + kHeader;
-  const int* trie_parent = reinterpret_cast<const int*>(beam + (size_t)kFields * W);
+  const int* trie_parent = reinterpret_cast<const int*>(beam + (size_t)kFieldsOf<kLM> * W);
   const int* trie_label = trie_parent + cap;
   const int nb = min(max(hdr[0], 1), W);
   if (i == 0) n_hyp[b] = min(N, nb);
@@ -502,9 +631,11 @@ __global__ __launch_bounds__(64) void ctc_beam_nbest_kernel(const unsigned* __re
   if (i >= nb) {
     count[row] = 0;
     log_prob[row] = neg_inf();
+    if constexpr (kLM) lm_score[row] = 0.f;
     return;
   }
   log_prob[row] = log_sum_exp(__uint_as_float(beam[W + i]), __uint_as_float(beam[2 * W + i]));
+  if constexpr (kLM) lm_score[row] = __uint_as_float(beam[10 * W + i]);
   const int len = min(max((int)beam[4 * W + i], 0), max_frames);
   if (len > max_len) {
     count[row] = -1;
@@ -519,94 +650,165 @@ __global__ __launch_bounds__(64) void ctc_beam_nbest_kernel(const unsigned* __re
   count[row] = len;
 }
 
-bool shape_ok(int B, int C, int W, int max_frames) {
+bool shape_ok(int B, int C, int W, int max_frames, int fields) {
   return B >= 1 && C >= 2 && C <= kMaxC && W >= 1 && W <= kMaxW && max_frames >= 1 &&
-         state_words(W, max_frames) <= (size_t)0x7fffffff;
+         state_words(W, max_frames, fields) <= (size_t)0x7fffffff;
+}
+
+// The entry points' checks; what: the entry point's name in the message, fields: kFields
+// or kLmFields.
+#define SRF_BEAM_SHAPE(what, fields)                                                                                  \
+  SRF_REQUIRE(shape_ok(B, C, beam_width, max_frames, fields),                                                         \
+              "%s: need B >= 1, 2 <= C <= %d, 1 <= beam_width <= %d, max_frames >= 1 and a trie below 2^31 "          \
+              "words (B=%d C=%d beam_width=%d max_frames=%d)",                                                        \
+              what, kMaxC, kMaxW, B, C, beam_width, max_frames)
+
+#define SRF_BEAM_BYTES(what, fields)                                                                                  \
+  SRF_REQUIRE(state_bytes >= (size_t)B * state_words(beam_width, max_frames, fields) * 4,                             \
+              "%s: the state block holds %zu bytes, %zu are needed", what, state_bytes,                               \
+              (size_t)B * state_words(beam_width, max_frames, fields) * 4)
+
+size_t state_bytes_of(const char* what, int B, int C, int beam_width, int max_frames, int fields) {
+  if (!shape_ok(B, C, beam_width, max_frames, fields)) {
+    srf::set_error("%s: need B >= 1, 2 <= C <= %d, 1 <= beam_width <= %d, max_frames >= 1 and a "
+                   "trie below 2^31 words (B=%d C=%d beam_width=%d max_frames=%d)",
+                   what, kMaxC, kMaxW, B, C, beam_width, max_frames);
+    return 0;
+  }
+  return (size_t)B * state_words(beam_width, max_frames, fields) * 4;
+}
+
+template <bool kLM>
+int reset(const char* what, void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+          int* frames_pushed, void* stream) {
+  SRF_BEAM_SHAPE(what, kFieldsOf<kLM>);
+  SRF_REQUIRE(state && frames_pushed, "%s: null state / frames_pushed", what);
+  SRF_BEAM_BYTES(what, kFieldsOf<kLM>);
+  hipLaunchKernelGGL(ctc_beam_reset_kernel<kLM>, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned*>(state), beam_width, max_frames);
+  SRF_LAUNCH_CHECK(what);
+  *frames_pushed = 0;
+  return SRF_OK;
+}
+
+// lm: null for the unfused search
+int push(const char* what, void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int blank,
+         const float* logits, const int* n_valid, int n, const LmTables* lm, int* frames_pushed, void* stream) {
+  const int fields = lm ? kLmFields : kFields;
+  SRF_BEAM_SHAPE(what, fields);
+  SRF_REQUIRE(state && frames_pushed, "%s: null state / frames_pushed", what);
+  SRF_BEAM_BYTES(what, fields);
+  SRF_REQUIRE(blank >= 0 && blank < C, "%s: blank = %d outside [0, %d)", what, blank, C);
+  SRF_REQUIRE(n >= 0 && n_valid, "%s: need n >= 0 and n_valid (n=%d)", what, n);
+  SRF_REQUIRE(n == 0 || logits, "%s: null logits with n = %d", what, n);
+  if (lm) {
+    SRF_REQUIRE(lm->bonus && lm->next, "%s: null language-model table", what);
+    SRF_REQUIRE(lm->S >= 1 && (long long)lm->S * C < (1ll << 31),
+                "%s: need n_states >= 1 and n_states * C < 2^31 (n_states=%d C=%d)", what, lm->S, C);
+  }
+  SRF_REQUIRE(*frames_pushed >= 0 && (long long)*frames_pushed + n <= max_frames,
+              "%s: %d frames after %d pushed since the reset exceed max_frames = %d", what, n, *frames_pushed,
+              max_frames);
+  if (n == 0) return SRF_OK;
+  if (lm)
+    hipLaunchKernelGGL(ctc_beam_push_kernel<LmTables>, dim3((unsigned)B), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), static_cast<unsigned*>(state), logits, n_valid, n, C, blank,
+                       beam_width, max_frames, make_fastdiv((unsigned)C), *lm);
+  else
+    hipLaunchKernelGGL(ctc_beam_push_kernel<>, dim3((unsigned)B), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                       static_cast<unsigned*>(state), logits, n_valid, n, C, blank, beam_width, max_frames,
+                       make_fastdiv((unsigned)C));
+  SRF_LAUNCH_CHECK(what);
+  *frames_pushed += n;
+  return SRF_OK;
+}
+
+template <bool kLM>
+int best(const char* what, const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+         int* labels, int* count, float* log_prob, float* lm_score, void* stream) {
+  SRF_BEAM_SHAPE(what, kFieldsOf<kLM>);
+  SRF_REQUIRE(state && labels && count && log_prob && (lm_score || !kLM), "%s: null pointer argument", what);
+  SRF_BEAM_BYTES(what, kFieldsOf<kLM>);
+  hipLaunchKernelGGL(ctc_beam_best_kernel<kLM>, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned*>(state), beam_width, max_frames, labels, count, log_prob, lm_score);
+  SRF_LAUNCH_CHECK(what);
+  return SRF_OK;
+}
+
+template <bool kLM>
+int nbest(const char* what, const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int N,
+          int max_len, int* labels, int* count, float* log_prob, float* lm_score, int* n_hyp, void* stream) {
+  SRF_BEAM_SHAPE(what, kFieldsOf<kLM>);
+  SRF_REQUIRE(N >= 1 && N <= beam_width && max_len >= 1,
+              "%s: need 1 <= N <= beam_width and max_len >= 1 (N=%d beam_width=%d max_len=%d)", what, N, beam_width,
+              max_len);
+  SRF_REQUIRE(state && labels && count && log_prob && n_hyp && (lm_score || !kLM), "%s: null pointer argument", what);
+  SRF_BEAM_BYTES(what, kFieldsOf<kLM>);
+  hipLaunchKernelGGL(ctc_beam_nbest_kernel<kLM>, dim3((unsigned)B, (unsigned)((N + 63) / 64)), dim3(64), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const unsigned*>(state), beam_width, max_frames, N,
+                     max_len, labels, count, log_prob, lm_score, n_hyp);
+  SRF_LAUNCH_CHECK(what);
+  return SRF_OK;
 }
 
 }  // namespace
 
-#define SRF_BEAM_SHAPE(what)                                                                                          \
-  SRF_REQUIRE(shape_ok(B, C, beam_width, max_frames),                                                                 \
-              what ": need B >= 1, 2 <= C <= %d, 1 <= beam_width <= %d, max_frames >= 1 and a trie below 2^31 "       \
-                   "words (B=%d C=%d beam_width=%d max_frames=%d)",                                                   \
-              kMaxC, kMaxW, B, C, beam_width, max_frames)
-
-#define SRF_BEAM_STATE(what)                                                                                          \
-  do {                                                                                                                \
-    SRF_BEAM_SHAPE(what);                                                                                             \
-    SRF_REQUIRE(state && frames_pushed, what ": null state / frames_pushed");                                         \
-    SRF_REQUIRE(state_bytes >= (size_t)B * state_words(beam_width, max_frames) * 4,                                   \
-                what ": the state block holds %zu bytes, %zu are needed", state_bytes,                                \
-                (size_t)B * state_words(beam_width, max_frames) * 4);                                                 \
-  } while (0)
-
 extern "C" size_t srf_ctc_beam_state_bytes(int B, int C, int beam_width, int max_frames) {
-  if (!shape_ok(B, C, beam_width, max_frames)) {
-    srf::set_error("ctc_beam_state_bytes: need B >= 1, 2 <= C <= %d, 1 <= beam_width <= %d, max_frames >= 1 and a "
-                   "trie below 2^31 words (B=%d C=%d beam_width=%d max_frames=%d)",
-                   kMaxC, kMaxW, B, C, beam_width, max_frames);
-    return 0;
-  }
-  return (size_t)B * state_words(beam_width, max_frames) * 4;
+  return state_bytes_of("ctc_beam_state_bytes", B, C, beam_width, max_frames, kFields);
 }
 
 extern "C" int srf_ctc_beam_reset(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
                                   int* frames_pushed, void* stream) {
-  SRF_BEAM_STATE("ctc_beam_reset");
-  hipLaunchKernelGGL(ctc_beam_reset_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
-                     static_cast<unsigned*>(state), beam_width, max_frames);
-  SRF_LAUNCH_CHECK("ctc_beam_reset");
-  *frames_pushed = 0;
-  return SRF_OK;
+  return reset<false>("ctc_beam_reset", state, state_bytes, B, C, beam_width, max_frames, frames_pushed, stream);
 }
 
 extern "C" int srf_ctc_beam_push_n(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
                                    int blank, const float* logits, const int* n_valid, int n, int* frames_pushed,
                                    void* stream) {
-  SRF_BEAM_STATE("ctc_beam_push");
-  SRF_REQUIRE(blank >= 0 && blank < C, "ctc_beam_push: blank = %d outside [0, %d)", blank, C);
-  SRF_REQUIRE(n >= 0 && n_valid, "ctc_beam_push: need n >= 0 and n_valid (n=%d)", n);
-  SRF_REQUIRE(n == 0 || logits, "ctc_beam_push: null logits with n = %d", n);
-  SRF_REQUIRE(*frames_pushed >= 0 && (long long)*frames_pushed + n <= max_frames,
-              "ctc_beam_push: %d frames after %d pushed since the reset exceed max_frames = %d", n, *frames_pushed,
-              max_frames);
-  if (n == 0) return SRF_OK;
-  hipLaunchKernelGGL(ctc_beam_push_kernel, dim3((unsigned)B), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
-                     static_cast<unsigned*>(state), logits, n_valid, n, C, blank, beam_width, max_frames,
-                     make_fastdiv((unsigned)C));
-  SRF_LAUNCH_CHECK("ctc_beam_push");
-  *frames_pushed += n;
-  return SRF_OK;
+  return push("ctc_beam_push", state, state_bytes, B, C, beam_width, max_frames, blank, logits, n_valid, n, nullptr,
+              frames_pushed, stream);
 }
 
 extern "C" int srf_ctc_beam_best(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
                                  int* labels, int* count, float* log_prob, void* stream) {
-  SRF_BEAM_SHAPE("ctc_beam_best");
-  SRF_REQUIRE(state && labels && count && log_prob, "ctc_beam_best: null pointer argument");
-  SRF_REQUIRE(state_bytes >= (size_t)B * state_words(beam_width, max_frames) * 4,
-              "ctc_beam_best: the state block holds %zu bytes, %zu are needed", state_bytes,
-              (size_t)B * state_words(beam_width, max_frames) * 4);
-  hipLaunchKernelGGL(ctc_beam_best_kernel, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const unsigned*>(state), beam_width, max_frames, labels, count, log_prob);
-  SRF_LAUNCH_CHECK("ctc_beam_best");
-  return SRF_OK;
+  return best<false>("ctc_beam_best", state, state_bytes, B, C, beam_width, max_frames, labels, count, log_prob,
+                     nullptr, stream);
 }
 
 extern "C" int srf_ctc_beam_nbest(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
                                   int N, int max_len, int* labels, int* count, float* log_prob, int* n_hyp,
                                   void* stream) {
-  SRF_BEAM_SHAPE("ctc_beam_nbest");
-  SRF_REQUIRE(N >= 1 && N <= beam_width && max_len >= 1,
-              "ctc_beam_nbest: need 1 <= N <= beam_width and max_len >= 1 (N=%d beam_width=%d max_len=%d)", N,
-              beam_width, max_len);
-  SRF_REQUIRE(state && labels && count && log_prob && n_hyp, "ctc_beam_nbest: null pointer argument");
-  SRF_REQUIRE(state_bytes >= (size_t)B * state_words(beam_width, max_frames) * 4,
-              "ctc_beam_nbest: the state block holds %zu bytes, %zu are needed", state_bytes,
-              (size_t)B * state_words(beam_width, max_frames) * 4);
-  hipLaunchKernelGGL(ctc_beam_nbest_kernel, dim3((unsigned)B, (unsigned)((N + 63) / 64)), dim3(64), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const unsigned*>(state), beam_width, max_frames, N,
-                     max_len, labels, count, log_prob, n_hyp);
-  SRF_LAUNCH_CHECK("ctc_beam_nbest");
-  return SRF_OK;
+  return nbest<false>("ctc_beam_nbest", state, state_bytes, B, C, beam_width, max_frames, N, max_len, labels, count,
+                      log_prob, nullptr, n_hyp, stream);
+}
+
+extern "C" size_t srf_ctc_beam_lm_state_bytes(int B, int C, int beam_width, int max_frames) {
+  return state_bytes_of("ctc_beam_lm_state_bytes", B, C, beam_width, max_frames, kLmFields);
+}
+
+extern "C" int srf_ctc_beam_lm_reset(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                     int* frames_pushed, void* stream) {
+  return reset<true>("ctc_beam_lm_reset", state, state_bytes, B, C, beam_width, max_frames, frames_pushed, stream);
+}
+
+extern "C" int srf_ctc_beam_lm_push_n(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                      int blank, const float* logits, const int* n_valid, int n, const float* bonus,
+                                      const int* next, int n_states, int* frames_pushed, void* stream) {
+  const LmTables lm{bonus, next, n_states};
+  return push("ctc_beam_lm_push", state, state_bytes, B, C, beam_width, max_frames, blank, logits, n_valid, n, &lm,
+              frames_pushed, stream);
+}
+
+extern "C" int srf_ctc_beam_lm_best(const void* state, size_t state_bytes, int B, int C, int beam_width,
+                                    int max_frames, int* labels, int* count, float* score, float* lm_score,
+                                    void* stream) {
+  return best<true>("ctc_beam_lm_best", state, state_bytes, B, C, beam_width, max_frames, labels, count, score,
+                    lm_score, stream);
+}
+
+extern "C" int srf_ctc_beam_lm_nbest(const void* state, size_t state_bytes, int B, int C, int beam_width,
+                                     int max_frames, int N, int max_len, int* labels, int* count, float* score,
+                                     float* lm_score, int* n_hyp, void* stream) {
+  return nbest<true>("ctc_beam_lm_nbest", state, state_bytes, B, C, beam_width, max_frames, N, max_len, labels, count,
+                     score, lm_score, n_hyp, stream);
 }

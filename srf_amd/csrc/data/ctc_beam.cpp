@@ -13,6 +13,9 @@
 // over the beams kept at the previous frame, then the beam_width prefixes with the
 // largest P = P_b + P_nb are kept (ties: the earlier-created prefix).  Prefixes are
 // nodes of a trie, so a beam is an int and extension is a hash lookup.
+//
+// srf_ctc_beam_search_lm (include/srf_data_lm.h) is the same search with a language model
+// fused in: every extension also gets bonus[state of the prefix][c].
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -21,6 +24,7 @@
 #include <vector>
 
 #include "../../../include/srf_data.h"
+#include "../../../include/srf_data_lm.h"
 
 namespace {
 
@@ -43,12 +47,19 @@ struct Score {
   float total() const { return log_sum_exp(pb, pnb); }
 };
 
-}  // namespace
+// A fused language model (srf_ctc_beam_search_lm): per trie node the automaton's state and
+// the bonuses of the node's labels, added in label order.  Both are functions of the prefix,
+// so a node made again gets the values it had.
+struct Lm {
+  const float* bonus;
+  const int32_t* next;
+  std::vector<int> state{0};
+  std::vector<float> acc{0.f};
+};
 
-extern "C" int srf_ctc_beam_search(const float* logits, int T, int C, int blank, int beam_width, int32_t* out_labels,
-                                   int* out_len, float* out_log_prob) {
-  if (T < 0 || C < 2 || blank < 0 || blank >= C || beam_width < 1 || !out_len || (T > 0 && (!logits || !out_labels)))
-    return -1;
+// lm: null for the search without a language model
+int search(const float* logits, int T, int C, int blank, int beam_width, Lm* lm, int32_t* out_labels, int* out_len,
+           float* out_log_prob, float* out_lm_score) {
   std::vector<Node> nodes{{-1, -1}};
   std::unordered_map<uint64_t, int> child;   // (parent, label) -> node
   auto child_of = [&](int parent, int c) {
@@ -57,6 +68,11 @@ extern "C" int srf_ctc_beam_search(const float* logits, int T, int C, int blank,
     if (it != child.end()) return it->second;
     const int id = (int)nodes.size();
     nodes.push_back({parent, c});
+    if (lm) {
+      const size_t at = (size_t)lm->state[parent] * C + c;
+      lm->state.push_back(lm->next[at]);
+      lm->acc.push_back(lm->acc[parent] + lm->bonus[at]);
+    }
     child.emplace(key, id);
     return id;
   };
@@ -100,7 +116,10 @@ extern "C" int srf_ctc_beam_search(const float* logits, int T, int C, int blank,
         const float prev = (c == last) ? s.pb : tot;
         if (prev == kNegInf) continue;
         Score& d = at(child_of(n, c));
-        d.pnb = log_sum_exp(d.pnb, prev + lp[c]);
+        if (lm)
+          d.pnb = log_sum_exp(d.pnb, (prev + lp[c]) + lm->bonus[(size_t)lm->state[n] * C + c]);
+        else
+          d.pnb = log_sum_exp(d.pnb, prev + lp[c]);
       }
     }
     // keep the beam_width most probable prefixes (stable: creation order breaks ties)
@@ -125,5 +144,27 @@ extern "C" int srf_ctc_beam_search(const float* logits, int T, int C, int blank,
   *out_len = (int)rev.size();
   for (size_t i = 0; i < rev.size(); ++i) out_labels[i] = rev[rev.size() - 1 - i];
   if (out_log_prob) *out_log_prob = score[best].total();
+  if (lm && out_lm_score) *out_lm_score = lm->acc[beams[best]];
   return 0;
+}
+
+}  // namespace
+
+extern "C" int srf_ctc_beam_search(const float* logits, int T, int C, int blank, int beam_width, int32_t* out_labels,
+                                   int* out_len, float* out_log_prob) {
+  if (T < 0 || C < 2 || blank < 0 || blank >= C || beam_width < 1 || !out_len || (T > 0 && (!logits || !out_labels)))
+    return -1;
+  return search(logits, T, C, blank, beam_width, nullptr, out_labels, out_len, out_log_prob, nullptr);
+}
+
+extern "C" int srf_ctc_beam_search_lm(const float* logits, int T, int C, int blank, int beam_width, const float* bonus,
+                                      const int32_t* next, int n_states, int32_t* out_labels, int* out_len,
+                                      float* out_score, float* out_lm_score) {
+  if (T < 0 || C < 2 || blank < 0 || blank >= C || beam_width < 1 || !out_len || (T > 0 && (!logits || !out_labels)))
+    return -1;
+  if (!bonus || !next || n_states < 1 || (long long)n_states * C >= (1ll << 31)) return -1;
+  for (size_t i = 0; i < (size_t)n_states * C; ++i)
+    if (next[i] < 0 || next[i] >= n_states || !std::isfinite(bonus[i])) return -1;
+  Lm lm{bonus, next};
+  return search(logits, T, C, blank, beam_width, &lm, out_labels, out_len, out_score, out_lm_score);
 }

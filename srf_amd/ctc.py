@@ -150,6 +150,16 @@ BEAM_MAX_WIDTH = 128     # SRF_CTC_BEAM_MAX_WIDTH
 BEAM_MAX_CLASSES = 128   # SRF_CTC_BEAM_MAX_CLASSES
 
 
+def _check_lm(lm, n_classes, blank_index):
+    """A fused language model must be made for these classes and this blank."""
+    if lm is None:
+        return
+    if lm.n_classes != int(n_classes):
+        raise ValueError(f'the language model has {lm.n_classes} classes, the logits {n_classes}')
+    if lm.blank != int(blank_index):
+        raise ValueError(f'the language model was fused with blank {lm.blank}, the decoder uses {blank_index}')
+
+
 def _check_beam_range(n_classes, blank_index, beam_width):
     if not 2 <= int(n_classes) <= BEAM_MAX_CLASSES:
         raise ValueError(f'the device beam search takes 2 .. {BEAM_MAX_CLASSES} classes, got {n_classes}')
@@ -168,17 +178,25 @@ class BeamState:
     (list of label lists, numpy log probabilities) of the most probable prefixes so far
     and leaves the state as it is; ``reset()`` starts over.  At most ``max_frames``
     frames may be pushed between two resets.  The result is that of beam_search_decode
-    on the frames pushed, however they were cut into chunks."""
+    on the frames pushed, however they were cut into chunks.
 
-    def __init__(self, n_utts, n_classes, blank_index, beam_width=100, max_frames=4096, device='cuda'):
+    With ``lm`` (a ``srf_amd.lm.FusedLM`` for the same classes and blank, its tables on
+    this device) the language model is fused into the beam (srf_ctc_beam_lm_*, DESIGN.md
+    section 17): scores are log p_ctc + the prefix's bonuses, and ``best_device()`` returns
+    a fourth tensor, the accumulated bonus."""
+
+    def __init__(self, n_utts, n_classes, blank_index, beam_width=100, max_frames=4096, device='cuda', lm=None):
         _check_beam_range(n_classes, blank_index, beam_width)
         if int(n_utts) < 1 or int(max_frames) < 1:
             raise ValueError(f'need n_utts >= 1 and max_frames >= 1, got {n_utts} and {max_frames}')
         self.shape = (int(n_utts), int(n_classes), int(beam_width), int(max_frames))
         self.blank = int(blank_index)
         self.device = torch.device(device)
+        _check_lm(lm, self.shape[1], self.blank)
+        self.lm = lm
         self._pushed = ctypes.c_int(0)
-        self._state = torch.empty(ops.ctc_beam_state_bytes(*self.shape), device=self.device, dtype=torch.uint8)
+        n_bytes = ops.ctc_beam_state_bytes(*self.shape) if lm is None else ops.ctc_beam_lm_state_bytes(*self.shape)
+        self._state = torch.empty(n_bytes, device=self.device, dtype=torch.uint8)
         self.reset()
 
     @property
@@ -186,19 +204,30 @@ class BeamState:
         return self._pushed.value
 
     def reset(self):
-        ops.ctc_beam_reset(self._state, self.shape, self._pushed)
+        if self.lm is None:
+            ops.ctc_beam_reset(self._state, self.shape, self._pushed)
+        else:
+            ops.ctc_beam_lm_reset(self._state, self.shape, self._pushed)
 
     def push(self, logits, n_valid):
         n_valid = torch.as_tensor(n_valid).to(device=self.device, dtype=torch.int32).contiguous()
-        ops.ctc_beam_push(self._state, self.shape, self._pushed, logits.detach().float().contiguous(), n_valid,
-                          self.blank)
+        logits = logits.detach().float().contiguous()
+        if self.lm is None:
+            ops.ctc_beam_push(self._state, self.shape, self._pushed, logits, n_valid, self.blank)
+        else:
+            ops.ctc_beam_lm_push(self._state, self.shape, self._pushed, logits, n_valid, self.blank, self.lm.bonus,
+                                 self.lm.next)
 
     def best_device(self):
-        """(labels [B, max_frames] int32, count [B] int32, log_prob [B] float32), on the device."""
-        return ops.ctc_beam_best(self._state, self.shape)
+        """(labels [B, max_frames] int32, count [B] int32, log_prob [B] float32), on the
+        device; with a language model log_prob is the fused score and a fourth tensor,
+        lm_score [B] float32, the accumulated bonus."""
+        if self.lm is None:
+            return ops.ctc_beam_best(self._state, self.shape)
+        return ops.ctc_beam_lm_best(self._state, self.shape)
 
     def best(self):
-        labels, count, log_prob = self.best_device()
+        labels, count, log_prob = self.best_device()[:3]
         count = count.cpu().tolist()
         labels = labels[:, :max(count + [1])].cpu().tolist()
         return [labels[b][:count[b]] for b in range(self.shape[0])], log_prob.cpu().double().numpy()
@@ -214,7 +243,9 @@ class BeamState:
         max_len = self.shape[3] if max_len is None else int(max_len)
         if max_len < 1:
             raise ValueError(f'max_len must be at least 1, got {max_len}')
-        return NBest(*ops.ctc_beam_nbest(self._state, self.shape, int(n), max_len))
+        if self.lm is None:
+            return NBest(*ops.ctc_beam_nbest(self._state, self.shape, int(n), max_len))
+        return NBest(*ops.ctc_beam_lm_nbest(self._state, self.shape, int(n), max_len))
 
 
 class NBest:
@@ -223,10 +254,13 @@ class NBest:
     (0 past ``count``; -1 for a prefix longer than max_len), ``log_prob`` [B, N] float32
     (the beam's log(p_b + p_nb), non-increasing along N, -inf past ``count``) and
     ``count`` [B] int32, the hypotheses the beam held (at most N).  ``lists()`` is the
-    host view."""
+    host view.  From a beam with a fused language model ``log_prob`` is the ranking score,
+    log p_ctc + the bonuses, and ``lm_score`` [B, N] float32 the bonuses (0 past
+    ``count``); ``lm_score`` is None without a model."""
 
-    def __init__(self, labels, lengths, log_prob, count):
+    def __init__(self, labels, lengths, log_prob, count, lm_score=None):
         self.labels, self.lengths, self.log_prob, self.count = labels, lengths, log_prob, count
+        self.lm_score = lm_score
 
     def lists(self):
         """Per utterance a list of (label list, log probability), ``count`` long.  One
@@ -241,10 +275,11 @@ class NBest:
         return out
 
 
-def beam_search_nbest_device(logits, lengths, blank_index, beam_width, n):
+def beam_search_nbest_device(logits, lengths, blank_index, beam_width, n, lm=None):
     """The ``n`` best prefixes of a device beam search over logits [B, T, C] (one reset,
     one push, one N-best call), as an ``NBest`` on the device: nothing is copied to the
-    host.  ValueError outside 2 <= C <= 128, 1 <= n <= beam_width <= 128."""
+    host.  ValueError outside 2 <= C <= 128, 1 <= n <= beam_width <= 128.  ``lm``: a
+    ``FusedLM`` to fuse into the beam (``NBest.lm_score`` is then set)."""
     if not torch.is_tensor(logits) or logits.dim() != 3 or not logits.is_cuda:
         shape, where = tuple(getattr(logits, 'shape', ())), getattr(logits, 'device', 'the host')
         raise ValueError(f'logits must be a device tensor [B, T, C], got {shape} on {where}')
@@ -252,48 +287,63 @@ def beam_search_nbest_device(logits, lengths, blank_index, beam_width, n):
     _check_beam_range(C, blank_index, beam_width)
     if B < 1:
         raise ValueError('logits hold no utterance')
-    state = BeamState(B, C, blank_index, beam_width, max(T, 1), logits.device)
+    state = BeamState(B, C, blank_index, beam_width, max(T, 1), logits.device, lm=lm)
     state.push(logits, torch.as_tensor(lengths))
     return state.nbest(n)
 
 
-def beam_search_decode_device(logits, lengths, blank_index, beam_width=100):
+def beam_search_decode_device(logits, lengths, blank_index, beam_width=100, lm=None):
     """beam_search_decode on the device: one reset, one push and one best call of the HIP
     prefix beam search; the labels, counts and scores are copied to the host, the logits
     are not.  logits [B, T, C] on the device, 2 <= C <= 128, 1 <= beam_width <= 128
-    (ValueError otherwise); returns (list of label lists, numpy log probabilities)."""
+    (ValueError otherwise); returns (list of label lists, numpy log probabilities).
+    ``lm``: a ``FusedLM`` to fuse into the beam; the scores are then the fused ones."""
     if logits.dim() != 3 or not logits.is_cuda:
         raise ValueError(f'logits must be a device tensor [B, T, C], got {tuple(logits.shape)} on {logits.device}')
     B, T, C = logits.shape
     _check_beam_range(C, blank_index, beam_width)
     if B < 1:
         raise ValueError('logits hold no utterance')
-    state = BeamState(B, C, blank_index, beam_width, max(T, 1), logits.device)
+    state = BeamState(B, C, blank_index, beam_width, max(T, 1), logits.device, lm=lm)
     state.push(logits, torch.as_tensor(lengths))
     return state.best()
 
 
-def beam_search_decode(logits, lengths, blank_index, beam_width=100):
+def beam_search_decode(logits, lengths, blank_index, beam_width=100, lm=None, with_lm_score=False):
     """tf.nn.ctc_beam_search_decoder(time-major logits, lengths, beam_width,
     top_paths=1) as process_test_step calls it (trainer_sr.py:109-112), on the host
     prefix beam search of libsrf_data.so.  logits [B, T, C] batch-major (device or
-    host); returns (list of label lists, numpy log probabilities)."""
+    host); returns (list of label lists, numpy log probabilities).  With ``lm`` (a
+    ``FusedLM``) the search is srf_ctc_beam_search_lm, which defines the fused result, and
+    the scores are the fused ones; with_lm_score=True then appends the best prefixes'
+    accumulated bonuses (numpy) to the result."""
     from . import load_speech_data as lsd
+    if with_lm_score and lm is None:
+        raise ValueError('with_lm_score comes with lm')
     L = lsd.lib()
     x = np.ascontiguousarray(logits.detach().float().cpu().numpy())
     lens = [int(v) for v in torch.as_tensor(lengths).cpu().tolist()]
     B, T, C = x.shape
-    out, logp = [], np.zeros(B, np.float64)
+    _check_lm(lm, C, blank_index)
+    out, logp, lm_score = [], np.zeros(B, np.float64), np.zeros(B, np.float64)
     buf = np.zeros(max(T, 1), np.int32)
     n = ctypes.c_int()
-    lp = ctypes.c_float()
+    lp, lms = ctypes.c_float(), ctypes.c_float()
     for b in range(B):
         t = max(0, min(lens[b], T))
         row = x[b]
-        rc = L.srf_ctc_beam_search(row.ctypes.data, t, C, int(blank_index), int(beam_width), buf.ctypes.data,
-                                   ctypes.byref(n), ctypes.byref(lp))
+        if lm is None:
+            rc = L.srf_ctc_beam_search(row.ctypes.data, t, C, int(blank_index), int(beam_width), buf.ctypes.data,
+                                       ctypes.byref(n), ctypes.byref(lp))
+        else:
+            rc = L.srf_ctc_beam_search_lm(row.ctypes.data, t, C, int(blank_index), int(beam_width),
+                                          lm.bonus_host.ctypes.data, lm.next_host.ctypes.data, lm.n_states,
+                                          buf.ctypes.data, ctypes.byref(n), ctypes.byref(lp), ctypes.byref(lms))
         if rc != 0:
             raise ValueError(f'srf_ctc_beam_search: bad argument (T={t}, C={C}, blank={blank_index}, beam={beam_width})')
         out.append(buf[:n.value].tolist())
         logp[b] = lp.value
+        lm_score[b] = lms.value
+    if with_lm_score:
+        return out, logp, lm_score
     return out, logp

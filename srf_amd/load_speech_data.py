@@ -53,6 +53,10 @@ _SIGNATURES = {
     'srf_tfr_writer_close': (ctypes.c_int, [_vp]),
     'srf_ctc_beam_search': (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
 }
+# include/srf_data_lm.h: the host beam search with a fused language model
+_LM_SIGNATURES = {
+    'srf_ctc_beam_search_lm': (ctypes.c_int, [_vp] + [ctypes.c_int] * 4 + [_vp, _vp, ctypes.c_int] + [_vp] * 4),
+}
 
 _lib = None
 
@@ -67,7 +71,7 @@ def lib():
         if not os.path.exists(DATA_LIB_PATH):
             raise ImportError(f'{DATA_LIB_PATH} is missing: build it with `make -C srf_amd/csrc`')
         h = ctypes.CDLL(DATA_LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_LM_SIGNATURES.items()):
             fn = getattr(h, name)
             fn.restype = res
             fn.argtypes = args

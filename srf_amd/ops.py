@@ -822,6 +822,68 @@ def ctc_beam_nbest(state, shape, n, max_len, labels=None):
     return labels, count, log_prob, n_hyp
 
 
+def ctc_beam_lm_state_bytes(B, C, beam_width, max_frames):
+    """srf_ctc_beam_lm_state_bytes: the block of the search with a fused language model."""
+    n = _lib.lib().srf_ctc_beam_lm_state_bytes(int(B), int(C), int(beam_width), int(max_frames))
+    if n == 0:
+        _lib.check(-1, 'srf_ctc_beam_lm_state_bytes')
+    return n
+
+
+def ctc_beam_lm_reset(state, shape, frames_pushed):
+    """srf_ctc_beam_lm_reset; the arguments of ctc_beam_reset."""
+    _lib.check(_lib.lib().srf_ctc_beam_lm_reset(*_beam_state_args(state, shape), ctypes.byref(frames_pushed),
+                                                _stream()), 'srf_ctc_beam_lm_reset')
+
+
+def ctc_beam_lm_push(state, shape, frames_pushed, logits, n_valid, blank, bonus, next_state):
+    """srf_ctc_beam_lm_push_n: ctc_beam_push with the language model's tables bonus
+    [S, C] float32 and next_state [S, C] int32 (contiguous, on the device)."""
+    B, C = shape[0], shape[1]
+    n = logits.shape[1] if logits.dim() == 3 else -1
+    _check_dev('logits', logits, (B, n, C))
+    t = n_valid
+    if not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != (B,) or not t.is_contiguous():
+        raise ValueError(f'n_valid must be a contiguous int32 device tensor of shape ({B},)')
+    S = bonus.shape[0] if bonus.dim() == 2 else -1
+    _check_dev('bonus', bonus, (S, C))
+    _check_i32('next_state', next_state, (S, C))
+    args = _beam_state_args(state, shape)
+    _lib.check(_lib.lib().srf_ctc_beam_lm_push_n(*args, int(blank), _ptr(logits), _ptr(n_valid), n, _ptr(bonus),
+                                                 _ptr(next_state), S, ctypes.byref(frames_pushed), _stream()),
+               'srf_ctc_beam_lm_push_n')
+
+
+def ctc_beam_lm_best(state, shape):
+    """srf_ctc_beam_lm_best: (labels [B, max_frames] int32, count [B] int32, score [B]
+    float32, lm_score [B] float32) on the device; the state is left as it is."""
+    B, max_frames = shape[0], shape[3]
+    labels = torch.empty((B, max_frames), device=state.device, dtype=torch.int32)
+    count = torch.empty(B, device=state.device, dtype=torch.int32)
+    score = torch.empty(B, device=state.device, dtype=torch.float32)
+    lm_score = torch.empty(B, device=state.device, dtype=torch.float32)
+    _lib.check(_lib.lib().srf_ctc_beam_lm_best(*_beam_state_args(state, shape), _ptr(labels), _ptr(count), _ptr(score),
+                                               _ptr(lm_score), _stream()), 'srf_ctc_beam_lm_best')
+    return labels, count, score, lm_score
+
+
+def ctc_beam_lm_nbest(state, shape, n, max_len):
+    """srf_ctc_beam_lm_nbest: ctc_beam_nbest's (labels, count, score, n_hyp) and lm_score
+    [B, n] float32, as (labels, count, score, n_hyp, lm_score)."""
+    B = shape[0]
+    n, max_len = int(n), int(max_len)
+    dev = state.device
+    labels = torch.empty((B, max(n, 0), max(max_len, 0)), device=dev, dtype=torch.int32)
+    count = torch.empty((B, max(n, 0)), device=dev, dtype=torch.int32)
+    score = torch.empty((B, max(n, 0)), device=dev, dtype=torch.float32)
+    lm_score = torch.empty((B, max(n, 0)), device=dev, dtype=torch.float32)
+    n_hyp = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.check(_lib.lib().srf_ctc_beam_lm_nbest(*_beam_state_args(state, shape), n, max_len, _ptr(labels), _ptr(count),
+                                                _ptr(score), _ptr(lm_score), _ptr(n_hyp), _stream()),
+               'srf_ctc_beam_lm_nbest')
+    return labels, count, score, n_hyp, lm_score
+
+
 def mwer_loss_and_grad(logits, logit_len, hyp, hyp_len, n_hyp, err, blank, grad_scale, want_grad=True):
     """srf_mwer_loss: the expected error of each utterance over its hypothesis list and
     grad_scale * its logit gradient.  logits [B, T, C] float32, logit_len [B], hyp

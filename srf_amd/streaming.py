@@ -115,10 +115,12 @@ class StreamingRouter:
     over; ``lookahead`` is 2 + L * rpad output frames; ``hypotheses`` the greedy labels so
     far.  With ``beam_width`` (1 .. 128) every chunk's logits also extend a device beam
     search (ctc.BeamState, at most ``max_frames`` output frames per stream, 4096 by
-    default): ``beam_hypotheses`` and ``beam_scores`` are its result so far.  The model's
-    parameters and BatchNorm moving statistics are read, never written."""
+    default): ``beam_hypotheses`` and ``beam_scores`` are its result so far; with ``lm`` (a
+    ``srf_amd.lm.FusedLM``) that language model is fused into the beam and the scores are
+    the fused ones.  The model's parameters and BatchNorm moving statistics are read, never
+    written."""
 
-    def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None):
+    def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None, lm=None):
         if model.caps_type == 'einsum':
             raise ValueError('the einsum variant cannot stream: its positional encoding needs the absolute frame '
                              'index, which srf_primary_caps_fwd_ex does not take')
@@ -128,6 +130,8 @@ class StreamingRouter:
             raise ValueError(f'n_streams must be >= 1, got {n_streams}')
         if int(max_chunk) < 4 or int(max_chunk) % 4:
             raise ValueError(f'max_chunk must be a positive multiple of 4 input frames, got {max_chunk}')
+        if lm is not None and not beam_width:
+            raise ValueError('lm is fused into the beam search: it comes with a beam_width')
         self.model, self.B, self.max_chunk = model, int(n_streams), int(max_chunk)
         self.L, self.lpad, self.rpad = model.enc_num, model.lpad, model.rpad
         self.lookahead = 2 + self.L * self.rpad
@@ -143,7 +147,7 @@ class StreamingRouter:
         self._beam = None
         if beam_width:
             self._beam = ctc.BeamState(self.B, model.class_n, self.blank, beam_width,
-                                       4096 if max_frames is None else max_frames, self.device)
+                                       4096 if max_frames is None else max_frames, self.device, lm=lm)
         self._alloc()
         self.reset()
 

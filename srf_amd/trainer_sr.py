@@ -709,7 +709,7 @@ def process_valid_step(in_len_div, inputs, model, loss_state, blank_idx, *, erro
 
 @torch.no_grad()
 def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host', timestamps=False, *,
-                      score=None, word_separator=None, word_fold=None):
+                      score=None, word_separator=None, word_fold=None, lm=None):
     """trainer_sr.py:96-117: forward, then tf.nn.ctc_beam_search_decoder(beam_width,
     top_paths=1) on the host (srf_amd.ctc.beam_search_decode) or, with
     decoder='device', on the GPU (srf_amd.ctc.beam_search_decode_device); best-path
@@ -722,9 +722,12 @@ def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'
     target lengths; what is printed and returned stays.  With timestamps=True and
     word_separator (a label index; word_fold an optional fold table) returns (hyps, spans,
     word_spans): per utterance the (labels tuple, start, end) output-frame spans of its
-    words (srf_amd.ctc.Alignment.words)."""
+    words (srf_amd.ctc.Alignment.words).  With lm (a srf_amd.lm.FusedLM) the language model
+    is fused into the beam search of either decoder; it needs a beam width."""
     if decoder not in ('host', 'device'):
         raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
+    if lm is not None and not beam_width:
+        raise ValueError('lm is fused into the beam search: it comes with a beam_width')
     if word_separator is None and word_fold is not None:
         raise ValueError('word_fold comes with word_separator')
     if word_separator is not None and not timestamps:
@@ -734,9 +737,9 @@ def process_test_step(in_len_div, inputs, model, beam_width=None, decoder='host'
     y_pred = model(feats, input_lengths=inp_len, training=False)
     lens = inp_len.to(torch.int64) // in_len_div
     if beam_width and decoder == 'device':
-        hyps, _ = ctc.beam_search_decode_device(y_pred, lens, y_pred.shape[-1] - 1, beam_width)
+        hyps, _ = ctc.beam_search_decode_device(y_pred, lens, y_pred.shape[-1] - 1, beam_width, lm=lm)
     elif beam_width:
-        hyps, _ = ctc.beam_search_decode(y_pred, lens, y_pred.shape[-1] - 1, beam_width)
+        hyps, _ = ctc.beam_search_decode(y_pred, lens, y_pred.shape[-1] - 1, beam_width, lm=lm)
     else:
         hyps = ctc.greedy_decode(y_pred, lens, y_pred.shape[-1] - 1)
     for u, h in zip(utt_id, hyps):
