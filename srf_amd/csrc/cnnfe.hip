@@ -1245,6 +1245,221 @@ __global__ void conv2_wgrad_reduce_kernel(const float* __restrict__ part, int ns
     gkb[(size_t)tc * C + n - C] = s;
 }
 
+// ---------------------------------------------------------------- wgrad by output rows
+// SRF_CONV2_WGRAD_ROWS (A/B builds only): 1 = conv2_wgrad_rows_kernel where it applies
+// (F2 <= 32), 0 = gab_split_t_kernel + conv2_wgrad32_kernel everywhere.
+#ifndef SRF_CONV2_WGRAD_ROWS
+#define SRF_CONV2_WGRAD_ROWS 1
+#endif
+
+// One workgroup forms all nine taps of a contiguous range of output rows (b, t2) for
+// one half of the input channels: part[range][tap][cin][n] = sum over the range's
+// pixels of x(p, tap)[cin] g_ab[p][n], M = 32 cin, N = n (wave w owns [32w, 32w + 32)),
+// K = the row's F2 <= 32 pixels (two k-steps of 16; slots past F2 hold zeros in both
+// operands).  Nine accumulator tiles per wave.
+//   A image: a ring of four y1 rows, slot (t1 + pt2) & 3.  An output row reads
+//   t1 = 2 t2 - pt2 + {0, 1, 2}; consecutive rows share one, so a row stages two new
+//   ones (three at the start of an utterance or of the range).  Each y1 element is loaded
+//   once (one column x 8 channels per thread), BN1, mask and 2^b applied, split to two
+//   fp16 planes.  A slot holds the even and the odd columns c = f1 + pf2 as separate
+//   [33][32 cin] sub-images: tap df reads contiguous rows of one of them (0: even,
+//   1: odd, 2: even shifted by one) with ds_read_b64_tr_b16; the row stride of 16
+//   dwords keeps the four rows of a read on distinct banks.  Even row 32 is only ever
+//   padding and stays zero from the start.
+//   B image: the row's g_ab [pixel][128] scaled by 2^ea and split as gab_split_t_kernel
+//   does, natural rows of stride 160 halves (80 dwords: conflict-free), read transposed
+//   once per k-step and used by all nine taps.
+// The next row's global loads are issued before the current row's MFMAs and written to
+// LDS after them, between two barriers; the second workgroup of the CU (the other cin
+// half of the same range, same XCD) fills that gap.
+constexpr int kWrRanges = 256;             // row ranges (a multiple of 8); two workgroups each
+constexpr int kWrCh = 32;                  // cin per workgroup = halves per A image row
+constexpr int kWrSub = 33 * kWrCh;         // halves per sub-image
+constexpr int kWrSlot = 4 * kWrSub;        // [even|odd][plane]
+constexpr int kWrBStride = 160;            // halves per B image row
+constexpr int kWrBPlane = 32 * kWrBStride;
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv2_wgrad_rows_kernel(
+    const float* __restrict__ y1, const float* __restrict__ stats1, const int* __restrict__ inp_len,
+    const float* __restrict__ g_ab, Dims d, int rows_per, float* __restrict__ part, const float* __restrict__ gmax,
+    int ngmax) {
+  __shared__ __attribute__((aligned(16))) _Float16 As[4 * kWrSlot];
+  __shared__ __attribute__((aligned(16))) _Float16 Bs[2 * kWrBPlane];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  // blocks b and b + 8 share an XCD: the two cin halves of a range read g_ab through one L2
+  const int hc = (blockIdx.x >> 3) & 1, rg = (blockIdx.x & 7) + 8 * (blockIdx.x >> 4);
+  const int R = d.B * d.T2;
+  const int rbeg = (int)min((long long)R, (long long)rg * rows_per), rend = min(R, rbeg + rows_per);
+  for (int k = tid; k < 4 * kWrSlot / 8; k += 256) *reinterpret_cast<ch8*>(&As[8 * k]) = ch8{};
+  for (int k = tid; k < 2 * kWrBPlane / 8; k += 256) *reinterpret_cast<ch8*>(&Bs[8 * k]) = ch8{};
+  const int ea = gab_exp(gmax, ngmax);
+  const float sa = srf_exp2i(ea);
+  const float out_sc = stats1[4 * C + 1] * srf_exp2i(-ea);
+  __syncthreads();
+
+  // A staging task: column slot ac (f1 = ac - pf2), channels 32 hc + 8 aoc .. + 7
+  const int ac = tid >> 2, aoc = tid & 3;
+  const int af1 = ac - d.pf2;
+  const bool acol_ok = af1 >= 0 && af1 < d.F1;
+  const int af1c = min(max(af1, 0), d.F1 - 1);
+  const int a_lds = (ac & 1) * 2 * kWrSub + (ac >> 1) * kWrCh + 8 * aoc;
+  // B staging tasks: pixels bpx and bpx + 16, n = 8 bo .. + 7
+  const int bpx = tid >> 4, bo = tid & 15;
+  float scale[8], shift[8];
+  const float bsc = stats1[4 * C];   // 2^b (exact): the A operand is 2^b BN1(y1)
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    scale[k] = stats1[2 * C + 32 * hc + 8 * aoc + k] * bsc;
+    shift[k] = stats1[3 * C + 32 * hc + 8 * aoc + k] * bsc;
+  }
+  f4 xv[3][2], gv[2][2];
+  bool xok[3] = {false, false, false};
+  // rows t1 = 2 t2 - pt2 + dt of utterance b (dt = 0 only when the ring starts afresh) and g_ab row (b, t2)
+  auto load_row = [&](int b, int t2, bool fresh) {
+    const int alen1 = ceil_div_len(inp_len[b], 2);
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) {
+      if (dt == 0 && !fresh) continue;
+      const int t1 = 2 * t2 - d.pt2 + dt;
+      xok[dt] = acol_ok && t1 >= 0 && t1 < d.T1 && t1 < alen1;
+      const int t1c = min(max(t1, 0), d.T1 - 1);
+      const float* src = y1 + (((size_t)b * d.T1 + t1c) * d.F1 + af1c) * C + 32 * hc + 8 * aoc;
+      xv[dt][0] = *reinterpret_cast<const f4*>(src);
+      xv[dt][1] = *reinterpret_cast<const f4*>(src + 4);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int pxc = min(bpx + 16 * u, d.F2 - 1);
+      const float* src = g_ab + (((size_t)b * d.T2 + t2) * d.F2 + pxc) * 2 * C + 8 * bo;
+      gv[u][0] = *reinterpret_cast<const f4*>(src);
+      gv[u][1] = *reinterpret_cast<const f4*>(src + 4);
+    }
+  };
+  auto put_row = [&](int t2, bool fresh) {
+#pragma unroll
+    for (int dt = 0; dt < 3; ++dt) {
+      if (dt == 0 && !fresh) continue;
+      ch8 p1, p2;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float v = xok[dt] ? (k < 4 ? xv[dt][0][k] : xv[dt][1][k - 4]) * scale[k] + shift[k] : 0.f;
+        _Float16 h1, h2;
+        srf_split2h(v, h1, h2);
+        p1[k] = h1;
+        p2[k] = h2;
+      }
+      _Float16* dst = As + ((2 * t2 + dt) & 3) * kWrSlot + a_lds;
+      *reinterpret_cast<ch8*>(dst) = p1;
+      *reinterpret_cast<ch8*>(dst + kWrSub) = p2;
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int px = bpx + 16 * u;
+      const bool ok = px < d.F2;
+      ch8 p1, p2;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float v = ok ? (k < 4 ? gv[u][0][k] : gv[u][1][k - 4]) * sa : 0.f;
+        _Float16 h1, h2;
+        srf_split2h(v, h1, h2);
+        p1[k] = h1;
+        p2[k] = h2;
+      }
+      _Float16* dst = Bs + px * kWrBStride + 8 * bo;
+      *reinterpret_cast<ch8*>(dst) = p1;
+      *reinterpret_cast<ch8*>(dst + kWrBPlane) = p2;
+    }
+  };
+  // transposed reads as conv2_wgrad32_kernel: lane 16 g + 4 q + p reads image row
+  // 8 (g >> 1) + q (+ 4), columns 16 (g & 1) + 4 p .. + 3, and receives column
+  // 16 (g & 1) + (lane & 15) at rows 8 (g >> 1) + 0..7 (k = pixel)
+  const int gg = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
+  const int a_off = (8 * (gg >> 1) + qq) * kWrCh + 16 * (gg & 1) + 4 * pp;
+  const int b_off = (8 * (gg >> 1) + qq) * kWrBStride + 32 * wv + 16 * (gg & 1) + 4 * pp;
+  auto tr8 = [&](const _Float16* base, int stride) {
+    const ws4 lo = lds_tr16(base), hi = lds_tr16(base + 4 * stride);
+    return __builtin_bit_cast(ch8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+  };
+  cf16 acc[9];
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) acc[tap] = cf16{};
+  auto compute = [&](int t2) {
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) {
+      const ch8 b1 = tr8(Bs + b_off + 16 * kb * kWrBStride, kWrBStride);
+      const ch8 b2 = tr8(Bs + kWrBPlane + b_off + 16 * kb * kWrBStride, kWrBStride);
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int dt = tap / 3, df = tap - dt * 3;
+        const _Float16* img =
+            As + ((2 * t2 + dt) & 3) * kWrSlot + (df & 1) * 2 * kWrSub + ((df >> 1) + 16 * kb) * kWrCh + a_off;
+        const ch8 a1 = tr8(img, kWrCh);
+        const ch8 a2 = tr8(img + kWrSub, kWrCh);
+        cf16 cc = acc[tap];
+        cc = mfma32h(a2, b1, cc);   // small terms first
+        cc = mfma32h(a1, b2, cc);
+        cc = mfma32h(a1, b1, cc);
+        acc[tap] = cc;
+      }
+    }
+  };
+
+  int b = rbeg / d.T2, t2 = rbeg - b * d.T2;
+  if (rbeg < rend) {
+    load_row(b, t2, true);
+    put_row(t2, true);
+  }
+  __syncthreads();
+  for (int row = rbeg; row < rend; ++row) {
+    const bool more = row + 1 < rend;
+    const bool nfresh = t2 + 1 == d.T2;
+    const int nb = nfresh ? b + 1 : b, nt2 = nfresh ? 0 : t2 + 1;
+    if (more) load_row(nb, nt2, nfresh);
+    compute(t2);
+    __syncthreads();
+    if (more) put_row(nt2, nfresh);
+    __syncthreads();
+    b = nb;
+    t2 = nt2;
+  }
+  // C layout: col = n (32 wv + r), rows = cin 32 hc + 8 q + 4 h + v; a workgroup without rows leaves zeros
+  float* dst = part + ((size_t)rg * 9 * C + 32 * hc) * 2 * C + 32 * wv + r;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        dst[((size_t)tap * C + 8 * q + 4 * h + v) * 2 * C] = acc[tap][4 * q + v] * out_sc;
+}
+
+// conv2_wgrad_reduce_kernel for the kWrRanges slabs: a workgroup sums 128 consecutive
+// outputs, thread (g, j) the slabs g, g + 8, ... of outputs 4 j .. 4 j + 3 in order, then
+// the eight groups' sums in order (interleaved groups: a batch with few rows, whose
+// nonzero slabs are the first ones, is still summed as a shallow tree).
+__global__ __launch_bounds__(256) void conv2_wgrad_reduce_rows_kernel(const float* __restrict__ part,
+                                                                      float* __restrict__ gka,
+                                                                      float* __restrict__ gkb) {
+  static_assert(kWrRanges == 256 && (9 * C * 2 * C) % 128 == 0, "eight groups of 32 slabs");
+  __shared__ f4 sums[8][32];
+  const int j = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const size_t idx = (size_t)blockIdx.x * 128 + 4 * j;
+  const float* src = part + (size_t)g * 9 * C * 2 * C + idx;
+  f4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 8
+  for (int k = 0; k < 32; ++k) s += *reinterpret_cast<const f4*>(src + (size_t)8 * k * 9 * C * 2 * C);
+  sums[g][j] = s;
+  __syncthreads();
+  if (g != 0) return;
+  for (int k = 1; k < 8; ++k) s += sums[k][j];
+  const int n = (int)(idx % (2 * C));
+  const size_t tc = idx / (2 * C);   // tap*C + cin
+  float* dst = n < C ? gka + tc * C + n : gkb + tc * C + n - C;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) dst[k] = s[k];
+}
+
 // BN1 backward + maxout/dropout backward + stage-1 weight/bias gradient partials.
 // part[block][j][c], j = 0..8 conv a taps, 9..17 conv b taps, 18 bias a, 19 bias b.
 __global__ __launch_bounds__(256) void conv1_bwd_kernel(
@@ -1494,6 +1709,10 @@ constexpr int kBnBlocks = 1024;
 constexpr int kWgrad32SplitsMax = 128;
 // pixel splits of conv2_wgrad32_kernel (a multiple of 8)
 constexpr int kWgrad32Splits = 56;
+// conv2_wgrad_rows_kernel takes a row of at most 32 output pixels as one K chunk (then
+// F1 <= 64 and the column slots f1 + pf2 fit its 64 staging columns); wider inputs keep
+// conv2_wgrad32_kernel and its gsT3 planes
+inline bool wgrad_by_rows(const Dims& d) { return SRF_CONV2_WGRAD_ROWS && d.F2 <= 32; }
 
 BwdWs2 bwd_ws_layout(const Dims& d, void* base) {
   const size_t P1 = (size_t)d.B * d.T1 * d.F1, P2 = (size_t)d.B * d.T2 * d.F2;
@@ -1505,11 +1724,12 @@ BwdWs2 bwd_ws_layout(const Dims& d, void* base) {
   };
   const size_t obp = take((size_t)kBnBlocks * 2 * C * 4), os2 = take(2 * C * 4), os1 = take(2 * C * 4),
                oab = take(P2 * 2 * C * 4), obias = take((size_t)kBnBlocks * 2 * C * 4), ogx = take(P1 * C * 4),
-               owq = take((size_t)9 * 2 * C * C * 4), owp = take((size_t)kWgrad32SplitsMax * 9 * C * 2 * C * 4),
+               owq = take((size_t)9 * 2 * C * C * 4),
+               owp = take((size_t)std::max(kWgrad32SplitsMax, kWrRanges) * 9 * C * 2 * C * 4),
                oc1 = take((size_t)conv1_blocks(d) * 20 * C * 4), oc1s = take(20 * C * 4),
                oscr = take(srf::colsum_scratch_floats(std::max(conv1_blocks(d), kBnBlocks), 20 * C) * 4);
   const int P2p = (int)((P2 + kTpPx - 1) / kTpPx * kTpPx);
-  const size_t ogs3 = take((size_t)3 * 2 * C * P2p * 2);
+  const size_t ogs3 = take(wgrad_by_rows(d) ? 0 : (size_t)3 * 2 * C * P2p * 2);
   const size_t ogm = take((size_t)kBnBlocks * 4), ods = take((size_t)C * 4);
   char* b = static_cast<char*>(base);
   BwdWs2 w;
@@ -1607,7 +1827,16 @@ int srf_cnnfe_bwd_parts(int parts, const float* feats, const int* inp_len, int B
   }
   const WgDiv dv{make_fastdiv(d.F2), make_fastdiv(d.T2)};
   const int nsplit = kWgrad32Splits;
-  if (parts & SRF_CNNFE_BWD_WGRAD) {
+  if ((parts & SRF_CNNFE_BWD_WGRAD) && wgrad_by_rows(d)) {
+    // B T2 output rows in kWrRanges ranges of rows_per (the last ones may be short or empty)
+    const int rows_per = (d.B * d.T2 + kWrRanges - 1) / kWrRanges;
+    hipLaunchKernelGGL(conv2_wgrad_rows_kernel, dim3(2 * kWrRanges), dim3(256), 0, st, sv.y1, sv.stats1, inp_len,
+                       (const float*)w.g_ab, d, rows_per, w.wpart, (const float*)w.gmax, kBnBlocks);
+    SRF_LAUNCH_CHECK("conv2_wgrad_rows");
+    hipLaunchKernelGGL(conv2_wgrad_reduce_rows_kernel, dim3(9 * C * 2 * C / 128), dim3(256), 0, st, w.wpart, g_k1a,
+                       g_k1b);
+    SRF_LAUNCH_CHECK("conv2_wgrad_reduce_rows");
+  } else if (parts & SRF_CNNFE_BWD_WGRAD) {
     static_assert(kW2Chunk == kWgChunk, "wgrad splits are whole chunks");
     const int split_len = ((P2 + nsplit - 1) / nsplit + kWgChunk - 1) / kWgChunk * kWgChunk;
     hipLaunchKernelGGL(gab_split_t_kernel<true>, dim3(w.P2p / kTpPx), dim3(256), 0, st, w.g_ab, P2, w.P2p,
