@@ -17,7 +17,6 @@
 //                partials;
 //   bn_apply     writes the CapsulationLayer output mask2(BN2(y2)).
 #include <algorithm>
-#include <type_traits>
 #include <cmath>
 #include <cstdlib>
 
@@ -67,14 +66,11 @@ __device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, flo
   n = nn;
 }
 
-// Split-bf16 weight packing of stage 2 (defined with the split kernels below), run
+// Split-fp16 weight packing of stage 2 (defined with the split kernels below), run
 // by extra blocks of the conv1 forward / conv2_bwd_prep launches.
-constexpr int kPackW2Threads = 2 * C * 64;             // one wave per stage-2 output column n
-constexpr int kPackW2tThreads = 9 * C * (2 * C / 8);   // (tap, cin, n/8)
+constexpr int kPackW2Threads = 2 * C * 64;   // one wave per stage-2 output column n
 __device__ __forceinline__ void pack_w2_f16_body(int idx, const float* __restrict__ ka, const float* __restrict__ kb,
                                                  _Float16* __restrict__ wp2, float* __restrict__ wsc);
-__device__ __forceinline__ void pack_w2t_split_body(int idx, const float* __restrict__ ka,
-                                                    const float* __restrict__ kb, __bf16* __restrict__ wq3);
 __device__ __forceinline__ void pack_w2t_f16_body(int idx, const float* __restrict__ ka, const float* __restrict__ kb,
                                                   _Float16* __restrict__ wq2h, float* __restrict__ wdsc);
 constexpr int kPackW2tF16Threads = C * 64;   // one wave per data-gradient output column cin
@@ -305,27 +301,22 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
 // the B fragments (packed, pre-split weights, shared by both waves) are staged in
 // LDS, double-buffered, one k-block ahead.  The epilogue fuses bias, dropout, maxout,
 // mask and the BN2 Welford partials.
-typedef __bf16 cbf8 __attribute__((ext_vector_type(8)));
-typedef float cf16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ cf16 mfma32bf(const cbf8& a, const cbf8& b, const cf16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-typedef _Float16 ch8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ cf16 mfma32h(const ch8& a, const ch8& b, const cf16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void split8v(const float (&v)[8], cbf8& p1, cbf8& p2, cbf8& p3) {
+// Eight floats times the power-of-two scale sc -> the two fp16 planes of an MFMA operand.
+__device__ __forceinline__ void split2h8(const float (&v)[8], h8& p1, h8& p2, float sc = 1.f) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const __bf16 a1 = (__bf16)v[k];
-    const float r = v[k] - (float)a1;
-    const __bf16 a2 = (__bf16)r;
-    p1[k] = a1;
-    p2[k] = a2;
-    p3[k] = (__bf16)(r - (float)a2);
+    _Float16 h1, h2;
+    srf_split2h(v[k] * sc, h1, h2);
+    p1[k] = h1;
+    p2[k] = h2;
   }
+}
+// c + a b on the split planes, small terms first: a2 b1, a1 b2, a1 b1.
+__device__ __forceinline__ f16v mfma3h(const h8& a1, const h8& a2, const h8& b1, const h8& b2, f16v c) {
+  c = mfma32h(a2, b1, c);
+  c = mfma32h(a1, b2, c);
+  return mfma32h(a1, b1, c);
 }
 
 // Packed split-fp16 weights wp2[plane][tap][n][cin] (n = ab*C + cout) of 2^a_n k (one
@@ -358,7 +349,7 @@ __device__ __forceinline__ void pack_w2_f16_body(int idx, const float* __restric
   if (cin == 0) wsc[n] = srf_exp2i(-e);
 }
 
-constexpr int kC2BStride = 24;   // bf16 per output row of an LDS B k-block (16 + 8: conflict-free b128 reads)
+constexpr int kC2BStride = 24;   // halves per output row of an LDS B k-block (16 + 8: conflict-free b128 reads)
 constexpr int kC2Waves = 4;      // 32 pixels each: 128 pixels per workgroup
 constexpr int kC2Px = 32 * kC2Waves;
 constexpr int kC2BLoads = 2 * 2 * C * 2 / (64 * kC2Waves);   // 16-byte B loads per thread per k-block (2 planes)
@@ -390,21 +381,21 @@ __global__ __launch_bounds__(64 * kC2Waves) __attribute__((amdgpu_waves_per_eu(2
   const int alen1 = ceil_div_len(inp_len[ab], 2);
 
   // k-block kk = tap * 4 + kb: input channels [16 kb, 16 kb + 16)
-  auto load_b = [&](int kk, ch8 (&bv)[kC2BLoads]) {
+  auto load_b = [&](int kk, h8 (&bv)[kC2BLoads]) {
     const int tap = kk >> 2, kb = kk & 3;
 #pragma unroll
     for (int q = 0; q < kC2BLoads; ++q) {
       const int idx = q * 64 * kC2Waves + tid;
       const int pl = idx >> 8, rem = idx & 255, n = rem >> 1, half = rem & 1;
-      bv[q] = *reinterpret_cast<const ch8*>(wp2 + pl * plane + ((size_t)tap * 2 * C + n) * C + 16 * kb + 8 * half);
+      bv[q] = *reinterpret_cast<const h8*>(wp2 + pl * plane + ((size_t)tap * 2 * C + n) * C + 16 * kb + 8 * half);
     }
   };
-  auto store_b = [&](int buf, const ch8 (&bv)[kC2BLoads]) {
+  auto store_b = [&](int buf, const h8 (&bv)[kC2BLoads]) {
 #pragma unroll
     for (int q = 0; q < kC2BLoads; ++q) {
       const int idx = q * 64 * kC2Waves + tid;
       const int pl = idx >> 8, rem = idx & 255, n = rem >> 1, half = rem & 1;
-      *reinterpret_cast<ch8*>(&Bs[buf][pl][n * kC2BStride + 8 * half]) = bv[q];
+      *reinterpret_cast<h8*>(&Bs[buf][pl][n * kC2BStride + 8 * half]) = bv[q];
     }
   };
   auto load_a = [&](int kk, f4 (&av)[2], bool& ok) {
@@ -418,38 +409,33 @@ __global__ __launch_bounds__(64 * kC2Waves) __attribute__((amdgpu_waves_per_eu(2
     av[1] = *reinterpret_cast<const f4*>(src + 4);
   };
 
-  cf16 acc[4];
+  f16v acc[4];
 #pragma unroll
-  for (int nt = 0; nt < 4; ++nt) acc[nt] = cf16{};
+  for (int nt = 0; nt < 4; ++nt) acc[nt] = f16v{};
   // one k-block: A split from registers, B from LDS buffer buf, 12 MFMAs
   auto compute = [&](int kk, int buf, const f4 (&av)[2], bool aok) {
-    ch8 a1, a2;
+    h8 a1, a2;
     {
       const int c0 = 16 * (kk & 3) + 8 * h;
+      float v[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const float x = q < 4 ? av[0][q] : av[1][q - 4];
-        _Float16 h1, h2;
-        srf_split2h(aok ? x * ss[0][c0 + q] + ss[1][c0 + q] : 0.f, h1, h2);
-        a1[q] = h1;
-        a2[q] = h2;
+        v[q] = aok ? x * ss[0][c0 + q] + ss[1][c0 + q] : 0.f;
       }
+      split2h8(v, a1, a2);
     }
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       const int nrow = (nt >> 1) * C + 32 * (nt & 1) + r;   // nt: 0/1 conv a, 2/3 conv b
-      const ch8 b1 = *reinterpret_cast<const ch8*>(&Bs[buf][0][nrow * kC2BStride + 8 * h]);
-      const ch8 b2 = *reinterpret_cast<const ch8*>(&Bs[buf][1][nrow * kC2BStride + 8 * h]);
-      cf16 c = acc[nt];
-      c = mfma32h(a2, b1, c);
-      c = mfma32h(a1, b2, c);
-      c = mfma32h(a1, b1, c);
-      acc[nt] = c;
+      const h8 b1 = *reinterpret_cast<const h8*>(&Bs[buf][0][nrow * kC2BStride + 8 * h]);
+      const h8 b2 = *reinterpret_cast<const h8*>(&Bs[buf][1][nrow * kC2BStride + 8 * h]);
+      acc[nt] = mfma3h(a1, a2, b1, b2, acc[nt]);
     }
   };
   // software pipeline, two k-blocks ahead: at k-block kk the registers hold the
   // operands of kk + 1 (stored to LDS at the end of kk) and receive those of kk + 2
-  ch8 bvA[kC2BLoads], bvB[kC2BLoads];
+  h8 bvA[kC2BLoads], bvB[kC2BLoads];
   f4 avA[2], avB[2], avC[2];
   bool okA, okB, okC;
   load_b(0, bvA);
@@ -646,16 +632,12 @@ __global__ __launch_bounds__(256) void conv2_bwd_prep_kernel(
     const float* __restrict__ stats2, const float* __restrict__ gamma2, const float* __restrict__ bnsum2,
     const int* __restrict__ inp_len, Dims d, float drop_p, unsigned long long seed, const unsigned long long* __restrict__ seed_src, float* __restrict__ g_ab,
     float* __restrict__ part, int nprep, const float* __restrict__ pk_a, const float* __restrict__ pk_b,
-    __bf16* __restrict__ wq3, _Float16* __restrict__ wq2h, float* __restrict__ wdsc, float* __restrict__ gmax) {
-  // blocks past nprep pack the transposed split weights of the data gradient
-  // (split-fp16 planes + per-cin exponents when wq2h != nullptr, else split-bf16)
+    _Float16* __restrict__ wq2h, float* __restrict__ wdsc, float* __restrict__ gmax) {
+  // blocks past nprep pack the transposed split-fp16 weights of the data gradient
+  // and their per-cin exponents
   if ((int)blockIdx.x >= nprep) {
     const int idx = (blockIdx.x - nprep) * blockDim.x + threadIdx.x;
-    if (wq2h != nullptr) {
-      if (idx < kPackW2tF16Threads) pack_w2t_f16_body(idx, pk_a, pk_b, wq2h, wdsc);
-    } else if (idx < kPackW2tThreads) {
-      pack_w2t_split_body(idx, pk_a, pk_b, wq3);
-    }
+    if (idx < kPackW2tF16Threads) pack_w2t_f16_body(idx, pk_a, pk_b, wq2h, wdsc);
     return;
   }
   seed = srf_step_seed(seed, seed_src);
@@ -731,36 +713,17 @@ __global__ __launch_bounds__(256) void conv2_bwd_prep_kernel(
   if (threadIdx.x == 0 && gmax != nullptr) gmax[blockIdx.x] = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
 }
 
-// ---------------------------------------------------------------- dgrad (split-bf16 MFMA)
-// The data gradient on v_mfma_f32_32x32x16_bf16 with 3-term splits, structured as
-// conv2_fwd32_kernel: all four stride-parity classes in one launch (block ranges
-// cls.boff), a workgroup = 4 waves x 32 input pixels of one class, a wave owns its
-// 32 pixels x all 64 cin (two N-tiles).  K = taps of the class x 128 (n) in
-// k-blocks of 16; the A fragments (g_ab rows, split on the VALU) are gathered into
-// registers two k-blocks ahead, the packed pre-split B (wq3[plane][tap][cin][n]) is
-// staged in LDS, double-buffered.
+// ---------------------------------------------------------------- dgrad (split-fp16 MFMA)
+// The data gradient on v_mfma_f32_32x32x16_f16 with 2-term fp16 splits of power-of-two
+// scaled operands, structured as conv2_fwd32_kernel: all four stride-parity classes in
+// one launch (block ranges cls.boff), a workgroup = 4 waves x 32 input pixels of one
+// class, a wave owns its 32 pixels x all 64 cin (two N-tiles).  K = taps of the class
+// x 128 (n) in k-blocks of 16; the A fragments (g_ab rows, scaled and split on the
+// VALU) are gathered into registers two k-blocks ahead, the packed pre-split B
+// (wq2h[plane][tap][cin][n]) is staged in LDS, double-buffered.
 struct DgCls {
   int boff[5];   // first block of parity class (qt, qf) = (c >> 1, c & 1); boff[4] = grid
 };
-
-// wq3[plane][tap][cin][n] = split(k_{a|b}[tap][cin][n % C]), one thread per 8 n.
-__device__ __forceinline__ void pack_w2t_split_body(int idx, const float* __restrict__ ka,
-                                                    const float* __restrict__ kb, __bf16* __restrict__ wq3) {
-  // idx = (tap, cin, n/8)
-  const int n8 = idx % (2 * C / 8), cin = (idx / (2 * C / 8)) % C, tap = idx / (C * (2 * C / 8));
-  const int n = 8 * n8;
-  const float* k = (n < C ? ka : kb) + ((size_t)tap * C + cin) * C + (n % C);
-  float v[8];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) v[q] = k[q];
-  cbf8 p1, p2, p3;
-  split8v(v, p1, p2, p3);
-  const size_t plane = (size_t)9 * C * 2 * C;
-  const size_t o = ((size_t)tap * C + cin) * 2 * C + n;
-  *reinterpret_cast<cbf8*>(wq3 + o) = p1;
-  *reinterpret_cast<cbf8*>(wq3 + plane + o) = p2;
-  *reinterpret_cast<cbf8*>(wq3 + 2 * plane + o) = p3;
-}
 
 // wq2h[plane][tap][cin][n] = 2-term fp16 split of 2^e_cin k_{a|b}[tap][cin][n % C] (one
 // exponent per data-gradient output column cin, uniform over K = taps x n), and
@@ -799,10 +762,6 @@ __device__ __forceinline__ void pack_w2t_f16_body(int idx, const float* __restri
 constexpr int kD2Waves = 4;
 constexpr int kD2Px = 32 * kD2Waves;
 
-// H = true: 2-term fp16 splits of power-of-two scaled operands (A = 2^ea g_ab with ea
-// from conv2_bwd_prep's block maxima, reduced by every workgroup; B = 2^e_cin k from
-// pack_w2t_f16_body), three f16 MFMAs per k-block tile instead of six bf16 ones;
-// the epilogue multiplies column cin by 2^-ea wdsc[cin].
 // split exponent of g_ab (max|g_ab| < 2^14 after scaling) from conv2_bwd_prep's block
 // maxima; every thread of the block calls it (one barrier)
 __device__ __forceinline__ int gab_exp(const float* __restrict__ gmax, int n) {
@@ -818,16 +777,14 @@ __device__ __forceinline__ int gab_exp(const float* __restrict__ gmax, int n) {
   return srf_split_exp(m);
 }
 
-template <bool H>
+// A = 2^ea g_ab with ea from conv2_bwd_prep's block maxima, reduced by every workgroup;
+// B = 2^e_cin k from pack_w2t_f16_body; three f16 MFMAs per k-block tile; the epilogue
+// multiplies column cin by 2^-ea wdsc[cin].
 __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2))) void conv2_dgrad32_kernel(
-    const float* __restrict__ g_ab, const void* __restrict__ wqv, Dims d, DgCls cls, float* __restrict__ g_x1,
+    const float* __restrict__ g_ab, const _Float16* __restrict__ wq2h, Dims d, DgCls cls, float* __restrict__ g_x1,
     const float* __restrict__ gmax, int ngmax, const float* __restrict__ wdsc) {
-  using BT = std::conditional_t<H, _Float16, __bf16>;
-  using V8 = std::conditional_t<H, ch8, cbf8>;
-  constexpr int NPL = H ? 2 : 3;
-  constexpr int BCH = NPL * C * 2;   // 16-byte B chunks per k-block (planes x cin x halves)
-  const BT* __restrict__ wq3 = static_cast<const BT*>(wqv);
-  __shared__ __attribute__((aligned(16))) BT Bs[2][NPL][C * kC2BStride];
+  constexpr int BCH = 2 * C * 2;   // 16-byte B chunks per k-block (planes x cin x halves)
+  __shared__ __attribute__((aligned(16))) _Float16 Bs[2][2][C * kC2BStride];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -841,12 +798,8 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
   const int ntf = (3 - df0 + 1) / 2, ntt = (3 - dt0 + 1) / 2;
   const int nkb = ntt * ntf * 8;
   const size_t plane = (size_t)9 * C * 2 * C;
-  float sa = 1.f, inv_sa = 1.f;
-  if constexpr (H) {   // split exponent of g_ab: max over conv2_bwd_prep's block maxima
-    const int ea = gab_exp(gmax, ngmax);
-    sa = srf_exp2i(ea);
-    inv_sa = srf_exp2i(-ea);
-  }
+  const int ea = gab_exp(gmax, ngmax);   // max over conv2_bwd_prep's block maxima
+  const float sa = srf_exp2i(ea), inv_sa = srf_exp2i(-ea);
 
   // A row of this lane: class pixel q0 + 32 wv + r
   const int pa = q0 + 32 * wv + r;
@@ -857,22 +810,22 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
   auto tap_of = [&](int k) { return (dt0 + 2 * (k / ntf)) * 3 + df0 + 2 * (k % ntf); };
 
   constexpr int NBL = (BCH + 64 * kD2Waves - 1) / (64 * kD2Waves);
-  auto load_b = [&](int kk, V8 (&bv)[NBL]) {
+  auto load_b = [&](int kk, h8 (&bv)[NBL]) {
     const int tap = tap_of(kk >> 3), kb = kk & 7;
 #pragma unroll
     for (int q = 0; q < NBL; ++q) {
       const int idx = min(q * 64 * kD2Waves + tid, BCH - 1);
       const int pl = idx / (2 * C), rem = idx % (2 * C), cin = rem >> 1, half = rem & 1;
-      bv[q] = *reinterpret_cast<const V8*>(wq3 + pl * plane + ((size_t)tap * C + cin) * 2 * C + 16 * kb + 8 * half);
+      bv[q] = *reinterpret_cast<const h8*>(wq2h + pl * plane + ((size_t)tap * C + cin) * 2 * C + 16 * kb + 8 * half);
     }
   };
-  auto store_b = [&](int buf, const V8 (&bv)[NBL]) {
+  auto store_b = [&](int buf, const h8 (&bv)[NBL]) {
 #pragma unroll
     for (int q = 0; q < NBL; ++q) {
       const int idx = q * 64 * kD2Waves + tid;
       if (idx < BCH) {
         const int pl = idx / (2 * C), rem = idx % (2 * C), cin = rem >> 1, half = rem & 1;
-        *reinterpret_cast<V8*>(&Bs[buf][pl][cin * kC2BStride + 8 * half]) = bv[q];
+        *reinterpret_cast<h8*>(&Bs[buf][pl][cin * kC2BStride + 8 * half]) = bv[q];
       }
     }
   };
@@ -887,59 +840,27 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
     av[1] = *reinterpret_cast<const f4*>(src + 4);
   };
 
-  cf16 acc[2];
-  acc[0] = cf16{};
-  acc[1] = cf16{};
+  f16v acc[2];
+  acc[0] = f16v{};
+  acc[1] = f16v{};
   auto compute = [&](int buf, const f4 (&av)[2], bool aok) {
-    if constexpr (H) {
-      ch8 a1, a2;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const float v = aok ? (q < 4 ? av[0][q] : av[1][q - 4]) : 0.f;
-        _Float16 h1, h2;
-        srf_split2h(v * sa, h1, h2);
-        a1[q] = h1;
-        a2[q] = h2;
-      }
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const int nrow = 32 * nt + r;
-        const ch8 b1 = *reinterpret_cast<const ch8*>(&Bs[buf][0][nrow * kC2BStride + 8 * h]);
-        const ch8 b2 = *reinterpret_cast<const ch8*>(&Bs[buf][1][nrow * kC2BStride + 8 * h]);
-        cf16 cc = acc[nt];
-        cc = mfma32h(a2, b1, cc);   // small terms first
-        cc = mfma32h(a1, b2, cc);
-        cc = mfma32h(a1, b1, cc);
-        acc[nt] = cc;
-      }
-      return;
-    } else {
-    cbf8 a1, a2, a3;
+    h8 a1, a2;
     {
       float v[8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) v[q] = aok ? (q < 4 ? av[0][q] : av[1][q - 4]) : 0.f;
-      split8v(v, a1, a2, a3);
+      split2h8(v, a1, a2, sa);
     }
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
       const int nrow = 32 * nt + r;
-      const cbf8 b1 = *reinterpret_cast<const cbf8*>(&Bs[buf][0][nrow * kC2BStride + 8 * h]);
-      const cbf8 b2 = *reinterpret_cast<const cbf8*>(&Bs[buf][1][nrow * kC2BStride + 8 * h]);
-      const cbf8 b3 = *reinterpret_cast<const cbf8*>(&Bs[buf][2][nrow * kC2BStride + 8 * h]);
-      cf16 cc = acc[nt];
-      cc = mfma32bf(a3, b1, cc);
-      cc = mfma32bf(a1, b3, cc);
-      cc = mfma32bf(a2, b2, cc);
-      cc = mfma32bf(a2, b1, cc);
-      cc = mfma32bf(a1, b2, cc);
-      cc = mfma32bf(a1, b1, cc);
-      acc[nt] = cc;
-    }
+      const h8 b1 = *reinterpret_cast<const h8*>(&Bs[buf][0][nrow * kC2BStride + 8 * h]);
+      const h8 b2 = *reinterpret_cast<const h8*>(&Bs[buf][1][nrow * kC2BStride + 8 * h]);
+      acc[nt] = mfma3h(a1, a2, b1, b2, acc[nt]);
     }
   };
   // two k-blocks ahead, as conv2_fwd32_kernel (nkb is a multiple of 8)
-  V8 bvA[NBL], bvB[NBL];
+  h8 bvA[NBL], bvB[NBL];
   f4 avA[2], avB[2];
   bool okA, okB;
   load_b(0, bvA);
@@ -973,11 +894,7 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
     }
   }
   // epilogue: lane column r = cin (32 nt + r), rows = pixels 8q + 4h + v of the wave
-  float osc[2] = {1.f, 1.f};
-  if constexpr (H) {
-    osc[0] = inv_sa * wdsc[r];
-    osc[1] = inv_sa * wdsc[32 + r];
-  }
+  const float osc[2] = {inv_sa * wdsc[r], inv_sa * wdsc[32 + r]};
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -986,8 +903,8 @@ __global__ __launch_bounds__(64 * kD2Waves) __attribute__((amdgpu_waves_per_eu(2
       if (p >= Pc) continue;
       const int kf = p % nkf, kt = (p / nkf) % nkt, b = p / (nkf * nkt);
       float* dst = g_x1 + (((size_t)b * d.T1 + qt + 2 * kt) * d.F1 + qf + 2 * kf) * C + r;
-      dst[0] = H ? acc[0][4 * q + v] * osc[0] : acc[0][4 * q + v];
-      dst[32] = H ? acc[1][4 * q + v] * osc[1] : acc[1][4 * q + v];
+      dst[0] = acc[0][4 * q + v] * osc[0];
+      dst[32] = acc[1][4 * q + v] * osc[1];
     }
 }
 
@@ -1000,20 +917,18 @@ struct WgDiv {
   FastDiv f2, t2;
 };
 
-// ---------------------------------------------------------------- wgrad (split-bf16 MFMA)
-// g_ab [P2][n] -> pixel-minor split planes gsT3[plane][n][P2p] (zero past P2), the B
-// operand image of conv2_wgrad32_kernel: 64 pixels per workgroup through LDS.
+// ---------------------------------------------------------------- wgrad (split-fp16 MFMA)
+// g_ab [P2][n] -> the two pixel-minor fp16 planes gsT[plane][n][P2p] of 2^ea g_ab (ea as
+// conv2_dgrad32_kernel; zero past P2), the B operand image of conv2_wgrad32_kernel:
+// 64 pixels per workgroup through LDS.
 constexpr int kTpPx = 64;
-// H: two fp16 planes of 2^ea g_ab (ea as conv2_dgrad32_kernel) instead of three bf16
-template <bool H>
 __global__ __launch_bounds__(256) void gab_split_t_kernel(const float* __restrict__ g_ab, int P2, int P2p,
-                                                          void* __restrict__ gsTv, const float* __restrict__ gmax,
+                                                          _Float16* __restrict__ gsT, const float* __restrict__ gmax,
                                                           int ngmax) {
   __shared__ float tile[kTpPx][2 * C + 1];
   const int tid = threadIdx.x;
   const int p0 = blockIdx.x * kTpPx;
-  float sa = 1.f;
-  if constexpr (H) sa = srf_exp2i(gab_exp(gmax, ngmax));
+  const float sa = srf_exp2i(gab_exp(gmax, ngmax));
   for (int k = tid; k < kTpPx * (2 * C / 4); k += 256) {
     const int px = k / (2 * C / 4), q = k % (2 * C / 4);
     const int p = p0 + px;
@@ -1030,63 +945,40 @@ __global__ __launch_bounds__(256) void gab_split_t_kernel(const float* __restric
     float v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = tile[8 * o + k][n];
-    if constexpr (H) {
-      ch8 p1, p2;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        _Float16 h1, h2;
-        srf_split2h(v[k] * sa, h1, h2);
-        p1[k] = h1;
-        p2[k] = h2;
-      }
-      _Float16* dst = static_cast<_Float16*>(gsTv) + (size_t)n * P2p + p0 + 8 * o;
-      *reinterpret_cast<ch8*>(dst) = p1;
-      *reinterpret_cast<ch8*>(dst + plane) = p2;
-    } else {
-      cbf8 p1, p2, p3;
-      split8v(v, p1, p2, p3);
-      __bf16* dst = static_cast<__bf16*>(gsTv) + (size_t)n * P2p + p0 + 8 * o;
-      *reinterpret_cast<cbf8*>(dst) = p1;
-      *reinterpret_cast<cbf8*>(dst + plane) = p2;
-      *reinterpret_cast<cbf8*>(dst + 2 * plane) = p3;
-    }
+    h8 p1, p2;
+    split2h8(v, p1, p2, sa);
+    _Float16* dst = gsT + (size_t)n * P2p + p0 + 8 * o;
+    *reinterpret_cast<h8*>(dst) = p1;
+    *reinterpret_cast<h8*>(dst + plane) = p2;
   }
 }
 
-// Weight gradient on v_mfma_f32_32x32x16_bf16 with 3-term splits: per (tap, pixel
+// Weight gradient on v_mfma_f32_32x32x16_f16 with 2-term fp16 splits: per (tap, pixel
 // split) part[s][tap][cin][n] = sum_p x(p, tap)[cin] g_ab[p][n], M = cin (two
 // tiles), N = n (wave w owns n in [32w, 32w+32)), K = pixels in chunks of 32.
+// A = 2^b BN1(y1) with bn_finalize's exponent, B = the 2^ea g_ab planes of
+// gab_split_t_kernel; the partial sums leave unscaled by 2^-(b + ea).
 // The A image (BN1 + mask1 applied, split) is staged by the workgroup in LDS as
 // natural [plane][pixel][cin] rows (one pixel x 8 channels per thread: two float4
 // loads, one index decode) and read back transposed into the k = pixel operand with
 // ds_read_b64_tr_b16; double-buffered.  Each wave loads its B fragments (8 pixels of
-// one n, per plane) straight from gsT3, one chunk ahead.
+// one n, per plane) straight from gsT, one chunk ahead.
 constexpr int kW2Chunk = 32;
-constexpr int kW2AStride = 96;   // bf16 per pixel row of the A image (64 cin + 32: conflict-free tr reads)
+constexpr int kW2AStride = 96;   // halves per pixel row of the A image (64 cin + 32: conflict-free tr reads)
 
 typedef short ws4 __attribute__((ext_vector_type(4)));
 
-template <typename BT>
-__device__ __forceinline__ ws4 lds_tr16(const BT* p) {
+__device__ __forceinline__ ws4 lds_tr16(const _Float16* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) ws4*)(reinterpret_cast<uintptr_t>(p)));
 }
 
-// H = true: split-fp16 operands (A = 2^b BN1(y1) with bn_finalize's exponent, B = the
-// 2^ea g_ab planes of gab_split_t_kernel<true>), three f16 MFMAs per tile instead of
-// six bf16; the partial sums leave unscaled by 2^-(b + ea).
-template <bool H>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv2_wgrad32_kernel(
     const float* __restrict__ y1, const float* __restrict__ stats1, const int* __restrict__ inp_len,
-    const void* __restrict__ gsTv, int P2p, Dims d, WgDiv dv, int nsplit, int split_len, float* __restrict__ part,
+    const _Float16* __restrict__ gsT, int P2p, Dims d, WgDiv dv, int nsplit, int split_len, float* __restrict__ part,
     const float* __restrict__ gmax, int ngmax) {
-  using BT = std::conditional_t<H, _Float16, __bf16>;
-  using V8 = std::conditional_t<H, ch8, cbf8>;
-  constexpr int NPL = H ? 2 : 3;
-  const BT* __restrict__ gsT3 = static_cast<const BT*>(gsTv);
-  __shared__ __attribute__((aligned(16))) BT As[2][NPL][kW2Chunk * kW2AStride];
-  float out_sc = 1.f;
-  if constexpr (H) out_sc = stats1[4 * C + 1] * srf_exp2i(-gab_exp(gmax, ngmax));
+  __shared__ __attribute__((aligned(16))) _Float16 As[2][2][kW2Chunk * kW2AStride];
+  const float out_sc = stats1[4 * C + 1] * srf_exp2i(-gab_exp(gmax, ngmax));
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
   // XCD-aware order (nsplit % 8 == 0): the nine taps of one pixel split run back to
@@ -1100,7 +992,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   // staging task: pixel px of the chunk, channels 8 oc .. 8 oc + 7
   const int px = tid >> 3, oc = tid & 7;
   float scale[8], shift[8];
-  const float bsc = H ? stats1[4 * C] : 1.f;   // 2^b (exact): the H operand is 2^b BN1(y1)
+  const float bsc = stats1[4 * C];   // 2^b (exact): the A operand is 2^b BN1(y1)
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     scale[k] = stats1[2 * C + 8 * oc + k] * bsc;
@@ -1127,49 +1019,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 #pragma unroll
     for (int k = 0; k < 8; ++k) v[k] = xok ? (k < 4 ? xv[0][k] : xv[1][k - 4]) * scale[k] + shift[k] : 0.f;
     const int o = px * kW2AStride + 8 * oc;
-    if constexpr (H) {
-      ch8 p1, p2;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        _Float16 h1, h2;
-        srf_split2h(v[k], h1, h2);
-        p1[k] = h1;
-        p2[k] = h2;
-      }
-      *reinterpret_cast<ch8*>(&As[buf][0][o]) = p1;
-      *reinterpret_cast<ch8*>(&As[buf][1][o]) = p2;
-    } else {
-      cbf8 p1, p2, p3;
-      split8v(v, p1, p2, p3);
-      *reinterpret_cast<cbf8*>(&As[buf][0][o]) = p1;
-      *reinterpret_cast<cbf8*>(&As[buf][1][o]) = p2;
-      *reinterpret_cast<cbf8*>(&As[buf][2][o]) = p3;
-    }
+    h8 p1, p2;
+    split2h8(v, p1, p2);
+    *reinterpret_cast<h8*>(&As[buf][0][o]) = p1;
+    *reinterpret_cast<h8*>(&As[buf][1][o]) = p2;
   };
   // transposed A read: lane 16 g + 4 q + p reads pixel row 8 (g >> 1) + q (+ 4) of the
   // k-block, cin 16 (g & 1) + 4 p .. + 3 of the M-tile; it receives cin 16 (g & 1) + (lane & 15)
   // at pixels 8 (g >> 1) + 0..7 = the 32x32x16 A fragment (row = l & 31, k = 8 (l >> 5) + j)
   const int gg = lane >> 4, qq = (lane >> 2) & 3, pp = lane & 3;
   const int a_off = (8 * (gg >> 1) + qq) * kW2AStride + 16 * (gg & 1) + 4 * pp;
-  auto read_a = [&](const BT* img, int kb, int mt) {
-    const BT* base = img + a_off + 16 * kb * kW2AStride + 32 * mt;
+  auto read_a = [&](const _Float16* img, int kb, int mt) {
+    const _Float16* base = img + a_off + 16 * kb * kW2AStride + 32 * mt;
     const ws4 lo = lds_tr16(base), hi = lds_tr16(base + 4 * kW2AStride);
-    return __builtin_bit_cast(V8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    return __builtin_bit_cast(h8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   };
   // B fragments of this wave: n = 32 wv + r, pixels 16 kb + 8 h .. + 7 of the chunk
   const size_t bplane = (size_t)2 * C * P2p;
-  const BT* brow = gsT3 + (size_t)(32 * wv + r) * P2p + 8 * h;
-  V8 bc[2][NPL], bn[2][NPL];
-  auto load_bf = [&](int pc0, V8 (&bf)[2][NPL]) {
+  const _Float16* brow = gsT + (size_t)(32 * wv + r) * P2p + 8 * h;
+  h8 bc[2][2], bn[2][2];
+  auto load_bf = [&](int pc0, h8 (&bf)[2][2]) {
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-      for (int pl = 0; pl < NPL; ++pl) bf[kb][pl] = *reinterpret_cast<const V8*>(brow + pl * bplane + pc0 + 16 * kb);
+      for (int pl = 0; pl < 2; ++pl) bf[kb][pl] = *reinterpret_cast<const h8*>(brow + pl * bplane + pc0 + 16 * kb);
   };
 
-  cf16 acc[2];
-  acc[0] = cf16{};
-  acc[1] = cf16{};
+  f16v acc[2];
+  acc[0] = f16v{};
+  acc[1] = f16v{};
   const int nch = (pend - pbeg + kW2Chunk - 1) / kW2Chunk;
   if (nch > 0) {
     gather(pbeg);
@@ -1188,34 +1066,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
-        if constexpr (H) {
-          const ch8 a1 = read_a(As[buf][0], kb, mt);
-          const ch8 a2 = read_a(As[buf][1], kb, mt);
-          cf16 cc = acc[mt];
-          cc = mfma32h(a2, bc[kb][0], cc);   // small terms first
-          cc = mfma32h(a1, bc[kb][1], cc);
-          cc = mfma32h(a1, bc[kb][0], cc);
-          acc[mt] = cc;
-        } else {
-          const cbf8 a1 = read_a(As[buf][0], kb, mt);
-          const cbf8 a2 = read_a(As[buf][1], kb, mt);
-          const cbf8 a3 = read_a(As[buf][2], kb, mt);
-          cf16 cc = acc[mt];
-          cc = mfma32bf(a3, bc[kb][0], cc);
-          cc = mfma32bf(a1, bc[kb][2], cc);
-          cc = mfma32bf(a2, bc[kb][1], cc);
-          cc = mfma32bf(a2, bc[kb][0], cc);
-          cc = mfma32bf(a1, bc[kb][1], cc);
-          cc = mfma32bf(a1, bc[kb][0], cc);
-          acc[mt] = cc;
-        }
+        const h8 a1 = read_a(As[buf][0], kb, mt);
+        const h8 a2 = read_a(As[buf][1], kb, mt);
+        acc[mt] = mfma3h(a1, a2, bc[kb][0], bc[kb][1], acc[mt]);
       }
     if (more) {
       put(buf ^ 1);
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-        for (int pl = 0; pl < NPL; ++pl) bc[kb][pl] = bn[kb][pl];
+        for (int pl = 0; pl < 2; ++pl) bc[kb][pl] = bn[kb][pl];
     }
     __syncthreads();
   }
@@ -1291,8 +1151,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   const int hc = (blockIdx.x >> 3) & 1, rg = (blockIdx.x & 7) + 8 * (blockIdx.x >> 4);
   const int R = d.B * d.T2;
   const int rbeg = (int)min((long long)R, (long long)rg * rows_per), rend = min(R, rbeg + rows_per);
-  for (int k = tid; k < 4 * kWrSlot / 8; k += 256) *reinterpret_cast<ch8*>(&As[8 * k]) = ch8{};
-  for (int k = tid; k < 2 * kWrBPlane / 8; k += 256) *reinterpret_cast<ch8*>(&Bs[8 * k]) = ch8{};
+  for (int k = tid; k < 4 * kWrSlot / 8; k += 256) *reinterpret_cast<h8*>(&As[8 * k]) = h8{};
+  for (int k = tid; k < 2 * kWrBPlane / 8; k += 256) *reinterpret_cast<h8*>(&Bs[8 * k]) = h8{};
   const int ea = gab_exp(gmax, ngmax);
   const float sa = srf_exp2i(ea);
   const float out_sc = stats1[4 * C + 1] * srf_exp2i(-ea);
@@ -1336,11 +1196,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
       gv[u][1] = *reinterpret_cast<const f4*>(src + 4);
     }
   };
+  // (both splits written out: through split2h8 the compiler schedules this kernel differently)
   auto put_row = [&](int t2, bool fresh) {
 #pragma unroll
     for (int dt = 0; dt < 3; ++dt) {
       if (dt == 0 && !fresh) continue;
-      ch8 p1, p2;
+      h8 p1, p2;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float v = xok[dt] ? (k < 4 ? xv[dt][0][k] : xv[dt][1][k - 4]) * scale[k] + shift[k] : 0.f;
@@ -1350,14 +1211,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
         p2[k] = h2;
       }
       _Float16* dst = As + ((2 * t2 + dt) & 3) * kWrSlot + a_lds;
-      *reinterpret_cast<ch8*>(dst) = p1;
-      *reinterpret_cast<ch8*>(dst + kWrSub) = p2;
+      *reinterpret_cast<h8*>(dst) = p1;
+      *reinterpret_cast<h8*>(dst + kWrSub) = p2;
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int px = bpx + 16 * u;
       const bool ok = px < d.F2;
-      ch8 p1, p2;
+      h8 p1, p2;
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float v = ok ? (k < 4 ? gv[u][0][k] : gv[u][1][k - 4]) * sa : 0.f;
@@ -1367,8 +1228,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
         p2[k] = h2;
       }
       _Float16* dst = Bs + px * kWrBStride + 8 * bo;
-      *reinterpret_cast<ch8*>(dst) = p1;
-      *reinterpret_cast<ch8*>(dst + kWrBPlane) = p2;
+      *reinterpret_cast<h8*>(dst) = p1;
+      *reinterpret_cast<h8*>(dst + kWrBPlane) = p2;
     }
   };
   // transposed reads as conv2_wgrad32_kernel: lane 16 g + 4 q + p reads image row
@@ -1379,28 +1240,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
   const int b_off = (8 * (gg >> 1) + qq) * kWrBStride + 32 * wv + 16 * (gg & 1) + 4 * pp;
   auto tr8 = [&](const _Float16* base, int stride) {
     const ws4 lo = lds_tr16(base), hi = lds_tr16(base + 4 * stride);
-    return __builtin_bit_cast(ch8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    return __builtin_bit_cast(h8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   };
-  cf16 acc[9];
+  f16v acc[9];
 #pragma unroll
-  for (int tap = 0; tap < 9; ++tap) acc[tap] = cf16{};
+  for (int tap = 0; tap < 9; ++tap) acc[tap] = f16v{};
   auto compute = [&](int t2) {
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      const ch8 b1 = tr8(Bs + b_off + 16 * kb * kWrBStride, kWrBStride);
-      const ch8 b2 = tr8(Bs + kWrBPlane + b_off + 16 * kb * kWrBStride, kWrBStride);
+      const h8 b1 = tr8(Bs + b_off + 16 * kb * kWrBStride, kWrBStride);
+      const h8 b2 = tr8(Bs + kWrBPlane + b_off + 16 * kb * kWrBStride, kWrBStride);
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
         const int dt = tap / 3, df = tap - dt * 3;
         const _Float16* img =
             As + ((2 * t2 + dt) & 3) * kWrSlot + (df & 1) * 2 * kWrSub + ((df >> 1) + 16 * kb) * kWrCh + a_off;
-        const ch8 a1 = tr8(img, kWrCh);
-        const ch8 a2 = tr8(img + kWrSub, kWrCh);
-        cf16 cc = acc[tap];
-        cc = mfma32h(a2, b1, cc);   // small terms first
-        cc = mfma32h(a1, b2, cc);
-        cc = mfma32h(a1, b1, cc);
-        acc[tap] = cc;
+        const h8 a1 = tr8(img, kWrCh);
+        const h8 a2 = tr8(img + kWrSub, kWrCh);
+        acc[tap] = mfma3h(a1, a2, b1, b2, acc[tap]);
       }
     }
   };
@@ -1544,16 +1401,21 @@ struct FwdSaved {
   size_t bytes;
 };
 
-FwdSaved saved_layout(const Dims& d, void* base) {
-  const size_t P1 = (size_t)d.B * d.T1 * d.F1, P2 = (size_t)d.B * d.T2 * d.F2;
+// Offsets of consecutive regions of one buffer, each aligned to 256 bytes.
+struct Bump {
   size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
+  size_t take(size_t bytes) {
+    const size_t o = off;
     off += srf::align_up(bytes, 256);
     return o;
-  };
-  const size_t oy1 = take(P1 * C * 4), oy2 = take(P2 * C * 4), os1 = take(5 * C * 4), os2 = take(5 * C * 4),
-               osel1 = take(P1 * C), osel2 = take(P2 * C);
+  }
+};
+
+FwdSaved saved_layout(const Dims& d, void* base) {
+  const size_t P1 = (size_t)d.B * d.T1 * d.F1, P2 = (size_t)d.B * d.T2 * d.F2;
+  Bump bp;
+  const size_t oy1 = bp.take(P1 * C * 4), oy2 = bp.take(P2 * C * 4), os1 = bp.take(5 * C * 4),
+               os2 = bp.take(5 * C * 4), osel1 = bp.take(P1 * C), osel2 = bp.take(P2 * C);
   char* b = static_cast<char*>(base);
   FwdSaved s;
   s.y1 = (float*)(b + oy1);
@@ -1562,7 +1424,7 @@ FwdSaved saved_layout(const Dims& d, void* base) {
   s.stats2 = (float*)(b + os2);
   s.sel1 = (unsigned char*)(b + osel1);
   s.sel2 = (unsigned char*)(b + osel2);
-  s.bytes = off;
+  s.bytes = bp.off;
   return s;
 }
 
@@ -1582,7 +1444,7 @@ int bn_finalize(const float* part, int nparts, float* merged, const float* gamma
 }
 
 struct FwdWs {
-  float *part1, *part2, *wp, *merged;
+  float *part1, *part2, *merged;
   _Float16* wp2;   // split-fp16 packed stage-2 weights [2][tap][n][cin]
   float* wsc;      // their per-column exponents 2^-a_n [2C]
   float* ymax;     // conv1 block maxima of |y1|
@@ -1592,16 +1454,10 @@ struct FwdWs {
 FwdWs fwd_ws_layout(const Dims& d, void* base) {
   const size_t P2 = (size_t)d.B * d.T2 * d.F2;
   const size_t nb2 = (P2 + 63) / 64;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += srf::align_up(bytes, 256);
-    return o;
-  };
-  const size_t op1 = take((size_t)conv1_blocks(d) * 3 * C * 4), op2 = take(nb2 * 3 * C * 4),
-               owp = take((size_t)9 * 2 * C * C * 4), omg = take((size_t)kBnMerge * 3 * C * 4),
-               owp2 = take((size_t)2 * 9 * 2 * C * C * 2), owsc = take((size_t)2 * C * 4),
-               oym = take((size_t)conv1_blocks(d) * 4);
+  Bump bp;
+  const size_t op1 = bp.take((size_t)conv1_blocks(d) * 3 * C * 4), op2 = bp.take(nb2 * 3 * C * 4),
+               omg = bp.take((size_t)kBnMerge * 3 * C * 4), owp2 = bp.take((size_t)2 * 9 * 2 * C * C * 2),
+               owsc = bp.take((size_t)2 * C * 4), oym = bp.take((size_t)conv1_blocks(d) * 4);
   char* b = static_cast<char*>(base);
   FwdWs w;
   w.wp2 = (_Float16*)(b + owp2);
@@ -1610,8 +1466,7 @@ FwdWs fwd_ws_layout(const Dims& d, void* base) {
   w.merged = (float*)(b + omg);
   w.part1 = (float*)(b + op1);
   w.part2 = (float*)(b + op2);
-  w.wp = (float*)(b + owp);
-  w.bytes = off;
+  w.bytes = bp.off;
   return w;
 }
 
@@ -1697,10 +1552,11 @@ int srf_cnnfe_fwd(const float* feats, const int* inp_len, int B, int T, int feat
 
 namespace {
 struct BwdWs2 {
-  float *bnpart, *bnsum2, *bnsum1, *g_ab, *biaspart, *g_x1, *wq, *wpart, *c1part, *c1sum, *scratch;
-  __bf16* gsT3;   // split-bf16 g_ab planes, pixel-minor (conv2_wgrad32_kernel)
-  float* gmax;    // block maxima of |g_ab| (conv2_bwd_prep_kernel)
-  float* wdsc;    // 2^-e_cin of the split-fp16 transposed weights
+  float *bnpart, *bnsum2, *bnsum1, *g_ab, *biaspart, *g_x1, *wpart, *c1part, *c1sum, *scratch;
+  _Float16* wq2h;   // split-fp16 transposed stage-2 weights [2][tap][cin][n] (conv2_dgrad32_kernel)
+  _Float16* gsT;    // split-fp16 g_ab planes [2][n][P2p], pixel-minor (conv2_wgrad32_kernel)
+  float* gmax;      // block maxima of |g_ab| (conv2_bwd_prep_kernel)
+  float* wdsc;      // 2^-e_cin of the split-fp16 transposed weights
   int P2p;
   size_t bytes;
 };
@@ -1711,26 +1567,24 @@ constexpr int kWgrad32SplitsMax = 128;
 constexpr int kWgrad32Splits = 56;
 // conv2_wgrad_rows_kernel takes a row of at most 32 output pixels as one K chunk (then
 // F1 <= 64 and the column slots f1 + pf2 fit its 64 staging columns); wider inputs keep
-// conv2_wgrad32_kernel and its gsT3 planes
+// conv2_wgrad32_kernel and its gsT planes
 inline bool wgrad_by_rows(const Dims& d) { return SRF_CONV2_WGRAD_ROWS && d.F2 <= 32; }
 
 BwdWs2 bwd_ws_layout(const Dims& d, void* base) {
   const size_t P1 = (size_t)d.B * d.T1 * d.F1, P2 = (size_t)d.B * d.T2 * d.F2;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += srf::align_up(bytes, 256);
-    return o;
-  };
-  const size_t obp = take((size_t)kBnBlocks * 2 * C * 4), os2 = take(2 * C * 4), os1 = take(2 * C * 4),
-               oab = take(P2 * 2 * C * 4), obias = take((size_t)kBnBlocks * 2 * C * 4), ogx = take(P1 * C * 4),
-               owq = take((size_t)9 * 2 * C * C * 4),
-               owp = take((size_t)std::max(kWgrad32SplitsMax, kWrRanges) * 9 * C * 2 * C * 4),
-               oc1 = take((size_t)conv1_blocks(d) * 20 * C * 4), oc1s = take(20 * C * 4),
-               oscr = take(srf::colsum_scratch_floats(std::max(conv1_blocks(d), kBnBlocks), 20 * C) * 4);
+  Bump bp;
+  const size_t obp = bp.take((size_t)kBnBlocks * 2 * C * 4), os2 = bp.take(2 * C * 4), os1 = bp.take(2 * C * 4),
+               oab = bp.take(P2 * 2 * C * 4), obias = bp.take((size_t)kBnBlocks * 2 * C * 4),
+               ogx = bp.take(P1 * C * 4), owq = bp.take((size_t)2 * 9 * C * 2 * C * 2),
+               owp = bp.take((size_t)std::max(kWgrad32SplitsMax, kWrRanges) * 9 * C * 2 * C * 4),
+               oc1 = bp.take((size_t)conv1_blocks(d) * 20 * C * 4), oc1s = bp.take(20 * C * 4),
+               oscr = bp.take(srf::colsum_scratch_floats(std::max(conv1_blocks(d), kBnBlocks), 20 * C) * 4);
   const int P2p = (int)((P2 + kTpPx - 1) / kTpPx * kTpPx);
-  const size_t ogs3 = take(wgrad_by_rows(d) ? 0 : (size_t)3 * 2 * C * P2p * 2);
-  const size_t ogm = take((size_t)kBnBlocks * 4), ods = take((size_t)C * 4);
+  // Two planes of 2C rows of P2p halves.  gab_split_t_kernel writes up to plane + 127 P2p + P2p - 1, the
+  // last half of the region; conv2_wgrad32_kernel reads whole 32-pixel chunks of rows n <= 127 that begin
+  // below P2 at multiples of 32, so they end at or before P2p (a multiple of 64).
+  const size_t ogs = bp.take(wgrad_by_rows(d) ? 0 : (size_t)2 * 2 * C * P2p * 2);
+  const size_t ogm = bp.take((size_t)kBnBlocks * 4), ods = bp.take((size_t)C * 4);
   char* b = static_cast<char*>(base);
   BwdWs2 w;
   w.bnpart = (float*)(b + obp);
@@ -1739,16 +1593,16 @@ BwdWs2 bwd_ws_layout(const Dims& d, void* base) {
   w.g_ab = (float*)(b + oab);
   w.biaspart = (float*)(b + obias);
   w.g_x1 = (float*)(b + ogx);
-  w.wq = (float*)(b + owq);
+  w.wq2h = (_Float16*)(b + owq);
   w.wpart = (float*)(b + owp);
   w.c1part = (float*)(b + oc1);
   w.c1sum = (float*)(b + oc1s);
   w.scratch = (float*)(b + oscr);
-  w.gsT3 = (__bf16*)(b + ogs3);
+  w.gsT = (_Float16*)(b + ogs);
   w.gmax = (float*)(b + ogm);
   w.wdsc = (float*)(b + ods);
   w.P2p = P2p;
-  w.bytes = off;
+  w.bytes = bp.off;
   return w;
 }
 
@@ -1795,22 +1649,22 @@ int srf_cnnfe_bwd_parts(int parts, const float* feats, const int* inp_len, int B
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int P2 = d.B * d.T2 * d.F2;
-  __bf16* wq3 = reinterpret_cast<__bf16*>(w.wq);
-  _Float16* wq2h = reinterpret_cast<_Float16*>(w.wq);
   if (parts & SRF_CNNFE_BWD_PREP) {
-  // BN2: sums -> d(beta2) = sum dy, d(gamma2) = sum dy*xh
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(kBnBlocks), dim3(256), 0, st, g_out, sv.y2, sv.stats2, inp_len, d.B,
-                     d.T2, d.F2, 4, w.bnpart);
-  SRF_LAUNCH_CHECK("bn_bwd_reduce(2)");
-  if ((rc = srf::colsum(w.bnpart, kBnBlocks, 2 * C, w.bnsum2, w.scratch, st, srf::ColSplit{{g_beta1, g_gamma1, nullptr, nullptr}, {C, C, 0, 0}})))
-    return rc;
-  const int npack = (kPackW2tF16Threads + 255) / 256;
-  hipLaunchKernelGGL(conv2_bwd_prep_kernel, dim3(kBnBlocks + npack), dim3(256), 0, st, g_out, sv.y2, sv.sel2,
-                     sv.stats2, gamma1, w.bnsum2, inp_len, d, drop_p, seed, srf::seed_source(), w.g_ab, w.biaspart,
-                     kBnBlocks, k1a, k1b, wq3, wq2h, w.wdsc, w.gmax);
-  SRF_LAUNCH_CHECK("conv2_bwd_prep");
-  if ((rc = srf::colsum(w.biaspart, kBnBlocks, 2 * C, nullptr, w.scratch, st, srf::ColSplit{{g_b1a, g_b1b, nullptr, nullptr}, {C, C, 0, 0}})))
-    return rc;
+    // BN2: sums -> d(beta2) = sum dy, d(gamma2) = sum dy*xh
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(kBnBlocks), dim3(256), 0, st, g_out, sv.y2, sv.stats2, inp_len,
+                       d.B, d.T2, d.F2, 4, w.bnpart);
+    SRF_LAUNCH_CHECK("bn_bwd_reduce(2)");
+    if ((rc = srf::colsum(w.bnpart, kBnBlocks, 2 * C, w.bnsum2, w.scratch, st,
+                          srf::ColSplit{{g_beta1, g_gamma1, nullptr, nullptr}, {C, C, 0, 0}})))
+      return rc;
+    const int npack = (kPackW2tF16Threads + 255) / 256;
+    hipLaunchKernelGGL(conv2_bwd_prep_kernel, dim3(kBnBlocks + npack), dim3(256), 0, st, g_out, sv.y2, sv.sel2,
+                       sv.stats2, gamma1, w.bnsum2, inp_len, d, drop_p, seed, srf::seed_source(), w.g_ab,
+                       w.biaspart, kBnBlocks, k1a, k1b, w.wq2h, w.wdsc, w.gmax);
+    SRF_LAUNCH_CHECK("conv2_bwd_prep");
+    if ((rc = srf::colsum(w.biaspart, kBnBlocks, 2 * C, nullptr, w.scratch, st,
+                          srf::ColSplit{{g_b1a, g_b1b, nullptr, nullptr}, {C, C, 0, 0}})))
+      return rc;
   }
   // stage-2 data gradient (4 stride-parity classes, split transposed weights packed by
   // the bwd_prep launch) and weight gradient, both on split-fp16 operands
@@ -1821,8 +1675,9 @@ int srf_cnnfe_bwd_parts(int parts, const float* feats, const int* inp_len, int B
       const int Pc = d.B * ((d.T1 - qt + 1) / 2) * ((d.F1 - qf + 1) / 2);
       cls.boff[c + 1] = cls.boff[c] + (Pc + kD2Px - 1) / kD2Px;
     }
-    hipLaunchKernelGGL(conv2_dgrad32_kernel<true>, dim3(cls.boff[4]), dim3(64 * kD2Waves), 0, st, w.g_ab,
-                       (const void*)wq2h, d, cls, w.g_x1, (const float*)w.gmax, kBnBlocks, (const float*)w.wdsc);
+    hipLaunchKernelGGL(conv2_dgrad32_kernel, dim3(cls.boff[4]), dim3(64 * kD2Waves), 0, st, w.g_ab,
+                       (const _Float16*)w.wq2h, d, cls, w.g_x1, (const float*)w.gmax, kBnBlocks,
+                       (const float*)w.wdsc);
     SRF_LAUNCH_CHECK("conv2_dgrad32");
   }
   const WgDiv dv{make_fastdiv(d.F2), make_fastdiv(d.T2)};
@@ -1839,11 +1694,11 @@ int srf_cnnfe_bwd_parts(int parts, const float* feats, const int* inp_len, int B
   } else if (parts & SRF_CNNFE_BWD_WGRAD) {
     static_assert(kW2Chunk == kWgChunk, "wgrad splits are whole chunks");
     const int split_len = ((P2 + nsplit - 1) / nsplit + kWgChunk - 1) / kWgChunk * kWgChunk;
-    hipLaunchKernelGGL(gab_split_t_kernel<true>, dim3(w.P2p / kTpPx), dim3(256), 0, st, w.g_ab, P2, w.P2p,
-                       (void*)w.gsT3, (const float*)w.gmax, kBnBlocks);
+    hipLaunchKernelGGL(gab_split_t_kernel, dim3(w.P2p / kTpPx), dim3(256), 0, st, w.g_ab, P2, w.P2p, w.gsT,
+                       (const float*)w.gmax, kBnBlocks);
     SRF_LAUNCH_CHECK("gab_split_t");
-    hipLaunchKernelGGL(conv2_wgrad32_kernel<true>, dim3(9 * nsplit), dim3(256), 0, st, sv.y1, sv.stats1, inp_len,
-                       (const void*)w.gsT3, w.P2p, d, dv, nsplit, split_len, w.wpart, (const float*)w.gmax,
+    hipLaunchKernelGGL(conv2_wgrad32_kernel, dim3(9 * nsplit), dim3(256), 0, st, sv.y1, sv.stats1, inp_len,
+                       (const _Float16*)w.gsT, w.P2p, d, dv, nsplit, split_len, w.wpart, (const float*)w.gmax,
                        kBnBlocks);
     SRF_LAUNCH_CHECK("conv2_wgrad32");
     hipLaunchKernelGGL(conv2_wgrad_reduce_kernel, dim3((9 * C * 2 * C + 255) / 256), dim3(256), 0, st, w.wpart,

@@ -870,18 +870,12 @@ __global__ __launch_bounds__(256, DIN >= 32 ? (R >= 4 ? 2 : 3) : (R >= 4 ? 3 : 4
 #ifndef SRF_GW16S_LDSVEC
 #define SRF_GW16S_LDSVEC 2
 #endif
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 // 4 waves, two workgroups per CU (three, with a two-slot ring, measured slower; 8 waves,
 // one per CU, halving the j-group partial sums the flush adds into g_emb, also slower:
 // C4 7.83-7.86 vs 7.82-7.83 ms, r06j)
 constexpr int kGux16NW = 4;
 constexpr int kGux16Occ = 2;
-
-__device__ __forceinline__ f16v mfma32h(const h8& a, const h8& b, const f16v& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
 
 // Split by masking, four pairs -> the 8 halves of an MFMA operand: hi = a' with the low
 // 13 mantissa bits cleared (exact in fp16 in the normal range), lo = f16(a' - hi);

@@ -71,14 +71,9 @@ namespace {
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ f16v mfma32(const bf8& a, const bf8& b, const f16v& c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f16v mfma32h(const h8& a, const h8& b, const f16v& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
 __device__ __forceinline__ float exp2i(int e) { return srf_exp2i(e); }

@@ -117,6 +117,12 @@ __device__ __forceinline__ void srf_split2h(float a, _Float16& a1, _Float16& a2)
   a1 = (_Float16)a;
   a2 = (_Float16)(a - (float)a1);
 }
+// v_mfma_f32_32x32x16_f16 on the split planes: 8 halves of k per lane, 32x32 fp32 tile
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef float f16v __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ f16v mfma32h(const h8& a, const h8& b, const f16v& c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

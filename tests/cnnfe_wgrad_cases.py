@@ -34,7 +34,12 @@ CASES = {
     'feat41_rows3': (30, 100, [100, 100, 77, 51, 18, 3, 100, 64, 99, 42] * 3, 0.0, 41, 8),
     # F2 = 33: the other side of the predicate (gab_split_t + conv2_wgrad32_kernel)
     'feat129_old_path': (2, 10, [10, 7], 0.0, 129, 9),
+    # the same path with P2 = 64 rows x 33 = 2,112 a multiple of 64: the planes of g_ab have no padding, the last
+    # pixel of the last plane is the last element of their workspace region and gmax / wdsc follow it directly
+    'feat129_full_planes': (4, 64, [64, 64, 50, 64], 0.0, 129, 10),
 }
+
+PLANE_PX = 64         # kTpPx: the g_ab planes are padded to a multiple of it
 
 DROP_SEED = 77
 

@@ -43,7 +43,12 @@ def test_case_structure():
         assert sum(e > b for b, e in rr) == C[name][0] * T2 < wc.RANGES
     assert wc.dims(37, 123)[0] % 2 == 1 and wc.dims(40, 123)[0] % 2 == 0        # pt2 = 1 / pt2 = 0
     assert wc.dims(1, 41)[1] % 2 == 1 and wc.dims(1, 41)[3] == 11                 # pf2 = 1, F2 < 31
-    assert not wc.by_rows(129) and all(wc.by_rows(c[4]) for n, c in C.items() if n != 'feat129_old_path')
+    assert not wc.by_rows(129) and all(wc.by_rows(c[4]) for n, c in C.items() if not n.startswith('feat129'))
+    B, T, _, _, feat_dim, _ = C['feat129_full_planes']      # old path, g_ab planes without padding
+    _, _, T2, F2 = wc.dims(T, feat_dim)
+    assert not wc.by_rows(feat_dim) and (B * T2 * F2) % wc.PLANE_PX == 0
+    B, T, _, _, feat_dim, _ = C['feat129_old_path']         # and with padding
+    assert (B * wc.dims(T, feat_dim)[2] * wc.dims(T, feat_dim)[3]) % wc.PLANE_PX != 0
 
 
 @pytest.mark.gpu
@@ -55,7 +60,7 @@ def test_cnnfe_wgrad(cuda, name):
     pt2_1 0.26, 0.30 (0.29, 0.34); pt2_0_drop 0.43, 0.45 (0.44, 0.54);
     one_row 3.90, 2.23 (3.90, 2.23: bit-identical); three_rows 0.83, 0.76 (0.80, 0.76);
     feat41 0.87, 0.69 (0.70, 0.75); feat41_rows3 0.25, 0.27 (0.23, 0.29);
-    feat129_old_path 0.56, 0.55 in both (the same kernel).
+    feat129_old_path 0.56, 0.55 in both (the same kernel); feat129_full_planes 0.39, 0.46.
     The worst err / bound is 0.36 (one_row g_k1a) in both builds, so the old kernels pass
     the factor 4 with more than 2x headroom and it stands.  Per tensor the default build's
     error is 0.84 .. 1.25 times the old build's (largest: feat41 g_k1a, 1.52e-5 against
