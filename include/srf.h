@@ -666,6 +666,57 @@ typedef struct {
 } srf_stream_buf;
 int srf_stream_advance_n(const srf_stream_buf* bufs, int n_bufs, int B, void* stream);
 
+/* ---- Waveform front end: 16 kHz samples to 123-d fbank features -------------
+ * Replaces the Kaldi step of egs/script/fbank123.sh (compute-fbank-feats --num-mel-bins=40
+ * --sample-frequency=16000 --use-log-fbank=True --use-energy=True, add-deltas, CMVN as
+ * save_speech_data.py:163 applies it).  fp32 throughout; DESIGN.md section 18 has the
+ * definitions.  Samples are in int16 scale, int16 (is_int16 = 1) or float32.
+ *
+ * Framing (snip-edges): T(n) = 0 for n < 400, else 1 + (n - 400) / 160 (srf_fbank_num_frames);
+ * frame t is samples 160 t .. 160 t + 399 of its stream.
+ *
+ * tables: SRF table block of srf_fbank_table_floats() floats, filled on the host by
+ * srf_fbank_tables (Povey window, exp(-2 pi i k / 512) for k < 256, and per mel filter its
+ * first bin, bin count and weights; computed in double, rounded once) and copied to the
+ * device by the caller.
+ *
+ * srf_fbank_static: frames [t0, t1) of every stream.  samples [B][stride], of which
+ * columns [0, width) hold the global samples s0 .. s0 + width - 1; n_samples [B] (device)
+ * the streams' lengths; a stream has T_b = T(min(max(n_samples[b], 0), n_limit)) frames,
+ * n_limit <= s0 + width the samples that have arrived.  statics [B][Ts][41], row r = frame
+ * f0 + r: rows of frames t < T_b get [log energy | 40 log-mel values], rows of frames
+ * T_b <= t < t1 zeros.  dither = a > 0 adds a g to every sample, g a standard Gaussian
+ * (Box-Muller) keyed by (seed, b, global sample index), so overlapping frames and every
+ * chunking see the same noise; a = 0 adds nothing.  A frame's values depend on its 400
+ * samples only, not on the launch.  Refused before any launch: 160 t0 < s0, n_limit beyond
+ * the buffer, rows outside [0, Ts), t1 > 13421764.
+ *
+ * srf_fbank_deltas: frames [t0, t1) of feats [B][To][123], row r = frame o0 + r, from
+ * statics [B][Ts][41], row r = frame f0 + r.  T_b = min(max(n_frames[b], 0), t_limit).
+ * Rows t < T_b: [static | delta | delta-delta] with the taps [-2 -1 0 1 2] / 10 and their
+ * self-convolution, both applied to the statics at frame indices clamped to [0, T_b - 1];
+ * then, with cmvn_rows = 1 (mean, stdev [123]) or B ([B][123]),
+ * y = (x - mean + 1e-14) / (stdev + 1e-14).  Rows T_b <= t < t1: zeros.  The statics frames
+ * max(t0 - 4, 0) .. min(t1 + 3, t_limit - 1) must lie in the statics buffer.
+ *
+ * srf_fbank_stats: sums [2 D + 1] doubles (device) += [sum x | sum x^2 | frame count] over
+ * the rows t < min(n_frames[b], T) of feats [B][T][D].  One launch, one workgroup per
+ * dimension, no atomics; nothing is read back. */
+#define SRF_FBANK_FRAME_LEN 400
+#define SRF_FBANK_FRAME_SHIFT 160
+#define SRF_FBANK_MEL 40
+#define SRF_FBANK_STATIC 41
+#define SRF_FBANK_FEAT 123
+int srf_fbank_num_frames(int n_samples);
+size_t srf_fbank_table_floats(void);
+int srf_fbank_tables(float* tables, size_t n_floats);
+int srf_fbank_static(const void* samples, int is_int16, const int* n_samples, const float* tables, int B, int stride,
+                     int width, int s0, int n_limit, int t0, int t1, int f0, int Ts, float dither,
+                     unsigned long long seed, float* statics, void* stream);
+int srf_fbank_deltas(const float* statics, const int* n_frames, int B, int Ts, int f0, int t_limit, int t0, int t1,
+                     const float* mean, const float* stdev, int cmvn_rows, float* feats, int To, int o0, void* stream);
+int srf_fbank_stats(const float* feats, const int* n_frames, int B, int T, int D, double* sums, void* stream);
+
 /* ---- Fused Adam over one flat parameter buffer ----------------------------
  * Replaces the Keras Adam apply of trainer_sr.py:71 / train_helper.py:60-70:
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= alpha m / (sqrt(v) + eps),

@@ -163,6 +163,12 @@ _SIGNATURES = {
     'srf_mwer_workspace': (_c_size, [_c_int] * 5),
     'srf_mwer_loss': (_c_int, [_vp] * 6 + [_c_int] * 6 + [ctypes.c_float] + [_vp] * 5 + [_c_size, _vp]),
     'srf_stream_advance_n': (_c_int, [ctypes.POINTER(StreamBuf), _c_int, _c_int, _vp]),
+    'srf_fbank_num_frames': (_c_int, [_c_int]),
+    'srf_fbank_table_floats': (_c_size, []),
+    'srf_fbank_tables': (_c_int, [_vp, _c_size]),
+    'srf_fbank_static': (_c_int, [_vp, _c_int, _vp, _vp] + [_c_int] * 9 + [ctypes.c_float, ctypes.c_ulonglong, _vp, _vp]),
+    'srf_fbank_deltas': (_c_int, [_vp, _vp] + [_c_int] * 6 + [_vp, _vp, _c_int, _vp, _c_int, _c_int, _vp]),
+    'srf_fbank_stats': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     'srf_adam_step': (_c_int, [_vp, _vp, _vp, _vp, _c_size, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                ctypes.c_float, _vp]),
 }

@@ -15,6 +15,7 @@ enum SrfRngStream : unsigned {
   kStreamEncaps2 = 5,
   kStreamInput = 6,
   kStreamMid0 = 7,   // + routing layer index
+  kStreamDither = 0x100,   // fbank.hip: two uniforms per sample, keyed by (seed, stream row, sample index)
 };
 
 __host__ __device__ __forceinline__ uint32_t srf_mix32(uint32_t x) {

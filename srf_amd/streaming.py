@@ -23,6 +23,11 @@ the carry).  The routing buffers share one timeline -- local frame = global fram
 -- so a layer's LayerNorm writes straight into the next layer's buffer, and one launch
 (srf_stream_advance_n) slides them all.  Everything runs on the current stream under
 ``torch.no_grad()``: no side streams, no graph capture.
+
+With a front end (``frontend=``, srf_amd/fbank.py) ``push_audio`` takes samples instead of
+features.  The audio side adds its own lookahead: a feature frame
+is final once the 4 frames after it are complete, 40 ms plus the frame's own 25 ms after
+its first sample, and up to 3 final frames wait for their group of 4.
 """
 import torch
 
@@ -58,10 +63,11 @@ def stream_schedule(pushes, n_layers, rpad):
     return rows
 
 
-def check_ended(lengths, ended, pushed, n):
+def check_ended(lengths, ended, pushed, n, unit='frames'):
     """Validate one push's ``ended`` against the streams' declared lengths (None: not
     declared) and return the new list.  ``pushed`` frames came before this chunk of
-    ``n``; a declared length must lie in [pushed, pushed + n] and is declared once."""
+    ``n``; a declared length must lie in [pushed, pushed + n] and is declared once.
+    ``unit`` names what is counted in the messages (the audio path counts samples)."""
     if ended is None:
         return list(lengths)
     vals = [int(e) for e in (ended.tolist() if hasattr(ended, 'tolist') else ended)]
@@ -76,12 +82,27 @@ def check_ended(lengths, ended, pushed, n):
         if lengths[b] is not None:
             raise ValueError(f'stream {b}: its length was already declared ({lengths[b]})')
         if e < pushed:
-            raise ValueError(f'stream {b}: length {e} lies before this chunk (frames {pushed} .. {pushed + n}): '
-                             'its frames were already emitted unmasked; declare the end with the chunk it lies in')
+            raise ValueError(f'stream {b}: length {e} lies before this chunk ({unit} {pushed} .. {pushed + n}): '
+                             f'its {unit} were already emitted unmasked; declare the end with the chunk it lies in')
         if e > pushed + n:
-            raise ValueError(f'stream {b}: length {e} lies beyond this chunk (frames {pushed} .. {pushed + n})')
+            raise ValueError(f'stream {b}: length {e} lies beyond this chunk ({unit} {pushed} .. {pushed + n})')
         new[b] = e
     return new
+
+
+def audio_chunk_bound(max_chunk):
+    """Most samples one ``push_audio`` call takes: 160 * (max_chunk - 8).  n samples
+    complete at most n // 160 + 1 feature frames; the end of a stream releases the 4 frames
+    its delta-delta held back; at most 3 frames wait for their group of 4: n // 160 + 8
+    frames at the most, which one ``push`` of max_chunk frames must take."""
+    return 160 * (int(max_chunk) - 8)
+
+
+def check_audio_chunk(n, max_chunk):
+    bound = audio_chunk_bound(max_chunk)
+    if n > bound:
+        raise ValueError(f'push_audio takes at most 160 * (max_chunk - 8) = {bound} samples per call '
+                         f'(max_chunk = {max_chunk}), got {n}')
 
 
 class StreamOut:
@@ -118,9 +139,22 @@ class StreamingRouter:
     default): ``beam_hypotheses`` and ``beam_scores`` are its result so far; with ``lm`` (a
     ``srf_amd.lm.FusedLM``) that language model is fused into the beam and the scores are
     the fused ones.  The model's parameters and BatchNorm moving statistics are read, never
-    written."""
+    written.
 
-    def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None, lm=None):
+    With ``frontend`` (a ``srf_amd.fbank.Fbank``) the router also takes audio:
+    ``push_audio(samples [B, n], ended=None)`` extracts the features of the next n samples
+    of every stream (``fbank.FbankStream``), holds the final feature frames back to a
+    multiple of 4 and hands them to ``push``; ``ended`` is the sample-domain one (a stream's
+    total sample count if its end lies in this chunk, else -1), from which the frame-domain
+    one is derived.  The returned ``StreamOut`` is empty when no group of 4 frames became
+    final.  One call takes at most ``audio_chunk_bound(max_chunk)`` = 160 * (max_chunk - 8)
+    samples, so that one ``push`` of at most max_chunk frames takes what it completes, the
+    end-of-stream flush included; more raises ``ValueError``.  ``finish()`` flushes the front
+    end first, ``reset()`` resets it.  ``lookahead_audio_ms`` is what the audio side adds to
+    the model's lookahead: 4 feature frames (the delta-delta's reach, 40 ms) plus the
+    frame's own 25 ms."""
+
+    def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None, lm=None, frontend=None):
         if model.caps_type == 'einsum':
             raise ValueError('the einsum variant cannot stream: its positional encoding needs the absolute frame '
                              'index, which srf_primary_caps_fwd_ex does not take')
@@ -135,6 +169,16 @@ class StreamingRouter:
         self.model, self.B, self.max_chunk = model, int(n_streams), int(max_chunk)
         self.L, self.lpad, self.rpad = model.enc_num, model.lpad, model.rpad
         self.lookahead = 2 + self.L * self.rpad
+        # audio side: a feature frame is final 4 frames (10 ms each) after its own 25 ms
+        self.lookahead_audio_ms = 4 * 10 + 25 if frontend is not None else 0
+        self._fe = None
+        if frontend is not None:
+            from . import fbank
+            if model.feat_dim_in != fbank.N_FEAT:
+                raise ValueError(f'the front end makes {fbank.N_FEAT}-d features, the model reads {model.feat_dim_in}')
+            if audio_chunk_bound(max_chunk) < 1:
+                raise ValueError(f'a front end needs max_chunk >= 12 input frames, got {max_chunk}')
+            self._fe = fbank.FbankStream(frontend, int(n_streams), audio_chunk_bound(max_chunk))
         self.blank = model.class_n - 1
         self.device = model.flat_params.device
         # the routing buffers' timeline: the last layer's next frame D sits at local
@@ -190,6 +234,10 @@ class StreamingRouter:
         if self._beam is not None:
             self._beam.reset()
         self._beam_best = None  # (labels, scores) of the frames pushed so far, once fetched
+        if self._fe is not None:
+            self._fe.reset()
+        self._held = None       # final feature frames that wait for their group of 4
+        self._frame_len = [None] * self.B   # frame counts of the streams whose audio ended
 
     def _fetch_beam(self):
         if self._beam is None:
@@ -318,15 +366,64 @@ class StreamingRouter:
         with torch.no_grad():
             return self._step(feats.to(device=self.device, dtype=torch.float32), False)
 
+    def push_audio(self, samples, ended=None):
+        """samples [B, n] (int16 or float32, int16 scale), n <= audio_chunk_bound(max_chunk).
+        ``ended`` [B]: the total sample count of a stream whose end lies in this chunk,
+        else -1."""
+        if self._fe is None:
+            raise ValueError('this router takes features only: build it with a frontend')
+        if self._finished:
+            raise ValueError('push_audio after finish(): call reset() to start new utterances')
+        if samples.dim() == 2:
+            check_audio_chunk(samples.shape[1], self.max_chunk)
+        with torch.no_grad():
+            return self._push_frames(self._fe.push(samples, ended), False)
+
+    def _push_frames(self, new, flush):
+        """Final feature frames to ``push``, in groups of 4 (``flush``: all of them, zero
+        padded to a group), with the ends of the streams whose last frame is among them."""
+        from . import fbank
+        fe = self._fe
+        for b, e in enumerate(fe.lengths):
+            if e is not None and self._frame_len[b] is None:
+                self._frame_len[b] = fbank.n_frames(e)
+        held = new if self._held is None else torch.cat([self._held, new], dim=1)
+        flush = flush or all(e is not None for e in fe.lengths)
+        n = held.shape[1] if flush else held.shape[1] // 4 * 4
+        take, self._held = held[:, :n], held[:, n:]
+        if n == 0:   # nothing for the model yet; an end at frame 0 is declared with the first group
+            out = StreamOut(self, frames_final(self._pushed, self.L, self.rpad)[-1],
+                            torch.empty((self.B, 0, self.model.class_n), device=self.device, dtype=torch.float32))
+            out._labels, out._frames = [[] for _ in range(self.B)], [[] for _ in range(self.B)]
+            return out
+        if n % 4:
+            take = torch.cat([take, take.new_zeros((self.B, 4 - n % 4, take.shape[2]))], dim=1)
+        # a stream's end is declared with the chunk its last frame lies in
+        ended = [e if self._lengths[b] is None and e is not None and e <= self._pushed + take.shape[1] else -1
+                 for b, e in enumerate(self._frame_len)]
+        return self.push(take.contiguous(), ended if any(e >= 0 for e in ended) else None)
+
     def finish(self):
         """End of every stream: the frames still held back by the lookahead.  A stream
-        that never declared a length ends with the last pushed frame."""
+        that never declared a length ends with the last pushed frame.  With a front end,
+        the feature frames it still holds go through ``push`` first, and the returned
+        ``StreamOut`` covers both steps."""
         if self._finished:
             raise ValueError('finish() was already called: call reset() to start new utterances')
+        first = None
+        if self._fe is not None:
+            with torch.no_grad():
+                first = self._push_frames(self._fe.finish(), True)
         self._check_beam_room(0, True)
         with torch.no_grad():
             out = self._step(None, True)
         self._finished = True
+        if first is not None and first.logits.shape[1]:
+            self._fetch_labels()
+            both = StreamOut(self, first.t0, torch.cat([first.logits, out.logits], dim=1))
+            both._labels = [a + b for a, b in zip(first._labels, out._labels)]
+            both._frames = [a + b for a, b in zip(first._frames, out._frames)]
+            return both
         return out
 
     def _check_beam_room(self, n, finishing):
