@@ -60,8 +60,9 @@ int srf_route_dr_fwd(const float* emb, const float* W, const float* bias, int B,
                      int rpad, int J, int dout, int iters, int mask_first, int n_chunks, float* v_out,
                      float* saved, void* workspace, size_t workspace_bytes, void* stream);
 /* Coupling storage (the 32x32 split-fp16 path: din in {8, 16, 32} <= dout in {8, 16, 32},
- * J*dout <= 1024; 0 for other shapes or iters < 2): the couplings c^r and logZ^r
- * of the routing iterations r >= 1, written by srf_route_dr_fwd_ex when
+ * J*dout <= 1024; 0 for other shapes or iters < 2): the couplings c^r of the routing
+ * iterations r >= 1 (and, at an unchanged offset and size, the region that once held
+ * logZ^r: no longer written or read), written by srf_route_dr_fwd_ex when
  * couplings != NULL and read by srf_route_dr_bwd_ex / _bwd_data_ex, whose
  * backward routing passes then skip the logit and softmax recompute.  NULL
  * couplings: the plain entry points' behaviour (forward stores nothing, backward

@@ -21,9 +21,17 @@ for name in re.findall(r'^(_Z\w*route_(?:fwd|bwd)32_kernelILi32ELi32ELi[248]ELi4
     while not re.match(r'\.LBB\d+_\d+:', raw[hdr[0]]):
         hdr[0] -= 1
     lab = raw[hdr[0]].split(':')[0]
-    ends = [k for k, l in enumerate(raw) if 'branch' in l and l.strip().endswith(lab)]
-    lo, hi = min(hdr + ends), max(hdr + ends)
-    lines = [l.strip() for l in raw[lo:hi + 1] if l.startswith('\t') and not l.strip().startswith(';')]
+    # the loop's blocks in layout order: the header's and every block the compiler marks
+    # 'in Loop: Header=<it>'.  A latch block laid out ahead of the header (it falls through
+    # into it; the loop is entered by a branch to the header) belongs to the loop as well,
+    # and the cyclic walk below takes the blocks in the order they run.
+    mark = 'Header=' + lab.lstrip('.L') + ' '
+    lines, inloop = [], False
+    for l in raw:
+        if re.match(r'(\.LBB\d+_\d+:|; %bb\.\d+:)', l):
+            inloop = l.startswith(lab + ':') or mark in l
+        elif inloop and l.startswith('\t') and not l.strip().startswith(';'):
+            lines.append(l.strip())
     for k, l in enumerate(lines):
         if not l.startswith('global_load_lds'):
             continue

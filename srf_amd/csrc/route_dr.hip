@@ -2002,11 +2002,15 @@ __global__ void fwd_finish_kernel(const float* __restrict__ slab, SlabSplit sp, 
 }
 
 // gs = squash'(s)^T a with a = a_init (the upstream gradient of the last
-// iteration's v) or, for earlier iterations, a = A += sum of gVc slabs.
+// iteration's v) or, for earlier iterations, a = A + sum of gVc slabs, where
+// A = sum_{r' > r} gVc^{r'} is what the later passes left.  A moves only where it is
+// needed: a_in == nullptr after pass R - 1 (A would be 0: a is the slab sum alone),
+// a_out == nullptr after pass 1 (nothing reads A any more) and on the a_init launch.
+// a_in and a_out may be the same buffer (each thread reads its float4 before it writes).
 // zero4 / nz4: float4s zeroed by the same launch (the g_emb accumulator of the gu pass).
 template <int DOUT>
 __global__ void bwd_finish_kernel(const float* __restrict__ slab, SlabSplit sp, size_t FJD,
-                                  const float* __restrict__ a_init, float* __restrict__ A,
+                                  const float* __restrict__ a_init, const float* a_in, float* a_out,
                                   const float* __restrict__ s, float* __restrict__ gs, float* __restrict__ zero4,
                                   size_t nz4, float* __restrict__ zero1) {
   constexpr int Q = DOUT / 4;
@@ -2018,10 +2022,10 @@ __global__ void bwd_finish_kernel(const float* __restrict__ slab, SlabSplit sp, 
   f4 a;
   if (a_init) {
     a = ld4(a_init + off);
-    if (ok) st4(A + off, f4{0.f, 0.f, 0.f, 0.f});   // A starts at 0 (gradient via later logits)
   } else {
-    a = ld4(A + off) + sum_slab4(slab, sp, FJD, off);
-    if (ok) st4(A + off, a);
+    a = sum_slab4(slab, sp, FJD, off);
+    if (a_in) a = ld4(a_in + off) + a;
+    if (a_out && ok) st4(a_out + off, a);
   }
   const f4 sv = ld4(s + off);
   const float n2 = qsum<Q>((sv.x * sv.x + sv.y * sv.y) + (sv.z * sv.z + sv.w * sv.w));
@@ -2104,14 +2108,14 @@ void launch_fwd_finish(const DrGeom& g, const float* slab, const SlabSplit& sp, 
 }
 
 template <int D>
-void launch_bwd_finish(const DrGeom& g, const float* slab, const SlabSplit& sp, const float* a_init, float* A,
-                       const float* s, float* gs, hipStream_t st, float* zero = nullptr, size_t n_zero = 0,
-                       float* zero1 = nullptr) {
+void launch_bwd_finish(const DrGeom& g, const float* slab, const SlabSplit& sp, const float* a_init,
+                       const float* a_in, float* a_out, const float* s, float* gs, hipStream_t st,
+                       float* zero = nullptr, size_t n_zero = 0, float* zero1 = nullptr) {
   const size_t FJD = (size_t)g.F() * g.JD();
   const size_t nz4 = zero ? n_zero / 4 : 0;
   const size_t n = std::max(FJD / 4, nz4);
   hipLaunchKernelGGL((bwd_finish_kernel<D>), dim3((n + 255) / 256), dim3(256), 0, st, slab, sp, FJD, a_init,
-                     A, s, gs, zero, nz4, zero1);
+                     a_in, a_out, s, gs, zero, nz4, zero1);
 }
 
 // row tiles per wave in the gu pass (a wave must hold whole output capsules)
@@ -2405,7 +2409,7 @@ Gw2Plan gw2_plan(const DrGeom& g, GwPass kind) {
 // The coupling readers address their blocks through buffer descriptors with 32-bit
 // byte ranges and 32-bit offsets (route_gux_kernel's c / gL blocks over all
 // iterations, route_gw3_kernel's per-iteration s and gs slices, the forward's
-// c / logZ stores): past 2^31 bytes the forward stores nothing and the backward
+// c stores): past 2^31 bytes the forward stores nothing and the backward
 // recomputes the logits instead of reading wrapped offsets.
 inline bool couplings_ok(const DrGeom& g, const srf::Fwd32Cpl& cpl) {
   if (!use_fwd32(g) || g.iters < 2 || g.din > 32) return false;
@@ -2461,6 +2465,10 @@ void resolve(DrPlan& p, const DrGeom& g, int n_chunks, bool have_couplings) {
   w.A = take(F * JD);
   w.gs = take((size_t)g.iters * F * JD);
   w.slab = take((size_t)p.chunks * F * JD);
+  // (logZ, sigma) per frame and capsule: written by the recomputing backward pass
+  // (route_pass_kernel) for route_gu_kernel only.  The passes from stored couplings neither
+  // write nor read it; the region, like Fwd32Cpl::lz, keeps its place so that no
+  // workspace size or offset moves.
   w.stats = take((size_t)(g.iters - 1) * F * in_n * 2);
   w.gu_t = take(in_n * (size_t)g.NT() * 16 * Fp);
   w.xT = take(in_n * g.din * Fp);
@@ -2539,13 +2547,12 @@ int fwd_impl(const DrPlan& p, const float* emb, const float* W, const float* bia
       continue;
     }
     if (p.fwd32) {
-      float *cst = nullptr, *lzst = nullptr;
+      float* cst = nullptr;
       if (p.couplings && r > 0) {
         const size_t blk = (size_t)srf::fwd32_frame_stride(g.F()) * g.in_n();
         cst = couplings + cl.c + (size_t)(r - 1) * blk * p.JP();
-        lzst = couplings + cl.lz + (size_t)(r - 1) * blk;
       }
-      const int rc = srf::fwd32_pass(plan, g, r == 0, planes, scratch, vc, cst, lzst, st);
+      const int rc = srf::fwd32_pass(plan, g, r == 0, planes, scratch, vc, cst, st);
       if (rc) return rc;
     } else {
       dispatch_pass<D, MODE_FWD>(g, p.pc, p.chunks, emb, W, bias, r, vc, r == 0 ? bsum : nullptr, slab, nullptr, 1, st);
@@ -2617,35 +2624,38 @@ int bwd_impl(const DrPlan& p, const float* emb, const float* W, const float* bia
   const size_t FJD = (size_t)g.F() * g.JD();
   const int R = g.iters;
   // gs^{R-1} = squash'(s^{R-1}) g_v.  A accumulates sum_{r'>r} gVc^{r'}, the
-  // gradient of v^r for r < R-1 (those v reach the loss only through the logits).
+  // gradient of v^r for r < R-1 (those v reach the loss only through the logits): the
+  // finish after pass R-1 starts it from the slabs alone (no zeros stored and read back),
+  // the finish after pass 1 no longer stores it, so R = 2 never touches ws + w.A.
   // Iteration 0 needs no backward pass: Vc^0 = 0, so its couplings are uniform
   // and its logits carry no gradient.
   const bool p32 = p.couplings;   // B1 and the gx pass from the forward's stored couplings
   float* const gsv = ws + w.gs;
   const size_t n_emb = (size_t)g.F() * g.N * g.din;
   // with stored couplings this launch also zeroes g_emb (the gu pass accumulates into it)
-  launch_bwd_finish<D>(g, nullptr, uniform_split(1), g_v, ws + w.A, saved + (size_t)(2 * (R - 1)) * FJD,
+  launch_bwd_finish<D>(g, nullptr, uniform_split(1), g_v, nullptr, nullptr, saved + (size_t)(2 * (R - 1)) * FJD,
                        gsv + (size_t)(R - 1) * FJD, st, p32 ? g_emb : nullptr, n_emb, p32 ? ws + w.gumax : nullptr);
   SRF_LAUNCH_CHECK("bwd_finish");
   for (int r = R - 1; r >= 1; --r) {
     const float* vc = saved + (size_t)(2 * (r - 1) + 1) * FJD;
-    float* stats_r = ws + w.stats + (size_t)(r - 1) * g.F() * g.in_n() * 2;
+    float* stats_r = ws + w.stats + (size_t)(r - 1) * g.F() * g.in_n() * 2;   // the recompute path's
+    const float* a_in = r == R - 1 ? nullptr : ws + w.A;
+    float* a_out = r == 1 ? nullptr : ws + w.A;
     if (p32) {
       // on the split-bf16 32x32 tiles, from the forward's operand planes
       const size_t blk = (size_t)srf::fwd32_frame_stride(g.F()) * g.in_n();
       const int JP = p.JP();
       const int rc = srf::bwd32_pass(plan, g, couplings + cl.planes, ws + w.p32,
-                                     couplings + cl.c + (size_t)(r - 1) * blk * JP,
-                                     couplings + cl.lz + (size_t)(r - 1) * blk, gsv + (size_t)r * FJD, stats_r,
+                                     couplings + cl.c + (size_t)(r - 1) * blk * JP, gsv + (size_t)r * FJD,
                                      ws + w.gl + (size_t)(r - 1) * blk * JP, st);
       if (rc) return rc;
-      launch_bwd_finish<D>(g, srf::fwd32_slab(plan, ws + w.p32), pass_split(g, plan), nullptr, ws + w.A,
+      launch_bwd_finish<D>(g, srf::fwd32_slab(plan, ws + w.p32), pass_split(g, plan), nullptr, a_in, a_out,
                            saved + (size_t)(2 * (r - 1)) * FJD, gsv + (size_t)(r - 1) * FJD, st);
     } else {
       dispatch_pass<D, MODE_BWD>(g, p.pc, p.chunks, emb, W, bias, r, vc, gsv + (size_t)r * FJD, ws + w.slab, stats_r, 1,
                                  st);
       SRF_LAUNCH_CHECK("route_pass(bwd)");
-      launch_bwd_finish<D>(g, ws + w.slab, uniform_split(p.chunks), nullptr, ws + w.A,
+      launch_bwd_finish<D>(g, ws + w.slab, uniform_split(p.chunks), nullptr, a_in, a_out,
                            saved + (size_t)(2 * (r - 1)) * FJD, gsv + (size_t)(r - 1) * FJD, st);
     }
     SRF_LAUNCH_CHECK("bwd_finish");

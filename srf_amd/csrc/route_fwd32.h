@@ -96,25 +96,28 @@ int fwd32_prepare(const Fwd32Plan& p, const DrGeom& g, const float* emb, const f
                   void* planes, void* scratch, float* WT, float* xT, hipStream_t st, bool wt16 = false,
                   bool xt16 = false);
 // one routing pass: partial s over i-chunks into fwd32_slab(p, scratch); passes r >= 1
-// also store the couplings c^r (cst) and logZ^r (lzst) when cst != nullptr.
+// also store the couplings c^r (cst) when cst != nullptr.
 int fwd32_pass(const Fwd32Plan& p, const DrGeom& g, bool first, const void* planes, void* scratch, const float* vc,
-               float* cst, float* lzst, hipStream_t st);
+               float* cst, hipStream_t st);
 // iteration 0 over all input capsules with the finish fused: writes s^0 (s_out),
 // Vc^1 = v^0 (vc_out) and, for one-iteration layers, v (v_out); din = dout = 32
 bool fwd32_first_full_supported(const Fwd32Shape& p, const DrGeom& g);
 int fwd32_first_full(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch, float* s_out,
                      float* vc_out, float* v_out, hipStream_t st);
 // Coupling storage of one training forward (float offsets): c^r [iters-1][in_n][JP][Fs],
-// logZ^r [iters-1][in_n][Fs], the operand planes, WT, xT; JP = JDp / dout,
+// lz [iters-1][in_n][Fs], the operand planes, WT, xT; JP = JDp / dout,
 // Fs = fwd32_frame_stride(F).  A function of the geometry alone (Fwd32Shape, above).
+// lz once held logZ^r of the softmax over j.  No pass writes or reads it any more (the
+// backward from stored couplings needs c^r alone); the region keeps its place so that
+// every offset behind it, and srf_route_dr_coupling_floats, stay what they were.
 struct Fwd32Cpl {
   size_t c, lz, planes, WT, xT, total;
 };
 Fwd32Cpl fwd32_cpl_layout(const Fwd32Shape& p, const DrGeom& g);
 // one backward routing pass r >= 1 from the stored couplings: partial gVc^r over
-// i-chunks into fwd32_slab(p, scratch), the (logZ, sigma) stats and the logit
-// gradients gL^r (glst, laid out as the couplings) of the gu pass
+// i-chunks into fwd32_slab(p, scratch) and the logit gradients gL^r (glst, laid out as
+// the couplings) of the gx / gW passes
 int bwd32_pass(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch, const float* cst,
-               const float* lz, const float* gs, float* stats, float* glst, hipStream_t st);
+               const float* gs, float* glst, hipStream_t st);
 
 }  // namespace srf

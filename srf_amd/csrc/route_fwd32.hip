@@ -617,9 +617,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, size_
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
 }
 
-// raw buffer store of one float; a voffset past the buffer drops it (no branch, so the
+// raw buffer store of one float; a zero-record descriptor drops it (no branch, so the
 // compiler's vmcnt bookkeeping stays exact)
-constexpr uint32_t kNoStore = 0x80000000u;
 __device__ __forceinline__ void bstore(__amdgpu_buffer_rsrc_t rs, float v, uint32_t voff, uint32_t soff) {
   __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), rs, voff, soff, 0);
 }
@@ -934,10 +933,9 @@ struct Args32 {
   const float* bsum;
   float* slab;
   // forward passes r >= 1: when cst != nullptr, the couplings c^r [in_n][JP][Fs]
-  // and logZ^r [in_n][Fs] (frame-minor: coalesced for every reader) are stored for
-  // the backward (route_bwd32_kernel reads them instead of recomputing the logits)
+  // (frame-minor: coalesced for every reader) are stored for the backward
+  // (route_bwd32_kernel reads them instead of recomputing the logits)
   float* cst;
-  float* lzst;
   int JP, Fs;
   // balanced split of the r >= 1 passes (bal_G > 0): workgroup w walks the units
   // [bal_first(w), bal_first(w + 1)) of bal_U = n_ftiles * in_n (route_fwd32.h)
@@ -1174,6 +1172,13 @@ template <int K = 0>
 __device__ __forceinline__ void xl_wait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(K) : "memory");
 }
+// vmcnt(0) as an instruction the compiler reads (xl_wait's asm it does not): ahead of a
+// capsule loop it tells the compiler that the prologue's operand loads have landed.  Left
+// to believe them in flight, it merges their order (bias of the last tile youngest) with
+// the loop's own at the loop header and waits vmcnt(0) at the first MFMAs of every pose.
+__device__ __forceinline__ void xl_wait_all() {
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), expcnt and lgkmcnt not waited for
+}
 
 // CPS capsules per stage buffer (one barrier per stage: CPS = 2 halves the barriers and
 // lets capsule 1's fragment reads ride under capsule 0's MFMAs; two buffers of two
@@ -1363,7 +1368,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   const Rsrc3 rs{make_rsrc(A.Ws, A.ws_bytes), make_rsrc(A.bs, A.bs_bytes), make_rsrc(A.xs, A.xs_bytes)};
   if (DIN <= 16 && NW > 1 && wv >= NW / 2) __builtin_amdgcn_s_setprio(1);   // din 32: measured faster without
   const __amdgpu_buffer_rsrc_t crs = make_rsrc(A.cst, A.cst ? (size_t)A.in_n * A.JP * A.Fs * 4 : 0);
-  const __amdgpu_buffer_rsrc_t lzs = make_rsrc(A.lzst, A.cst ? (size_t)A.in_n * A.Fs * 4 : 0);
 
   f4* vcl = reinterpret_cast<f4*>(lds) + (size_t)tbase * 4 * 64;   // wave's slab, from the SGPR tbase = wv * TW
   float2* st = reinterpret_cast<float2*>(lds + (size_t)NW * TW * 4 * 64 * 4);
@@ -1525,9 +1529,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         float2* slot = st + par * NW * 32;
         if (sh == 0) slot[wvu * 32 + sr] = make_float2(M, Z);
         // x of capsule i + 1 (DMA'd after the last barrier) lands before this one; the next
-        // capsule's W / bias loads (5 per tile) and the last capsule's coupling / logZ
-        // stores issued since may stay in flight (scripts/dbg/check_xl_wait4.py)
-        if constexpr (XJ) xl_wait<5 * TW + OWN + 1>();
+        // capsule's W / bias loads (5 per tile) and the last capsule's coupling stores
+        // issued since may stay in flight (scripts/dbg/check_xl_wait4.py)
+        if constexpr (XJ) xl_wait<5 * TW + OWN>();
         __syncthreads();
         // every wave's pose read x of capsule i: its buffer takes capsule i + 2's (unconditional:
         // past the chunk it reloads the last capsule into a buffer no pose reads any more)
@@ -1563,8 +1567,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         for (int a = 0; a < OWN; ++a)
           bstore(crs, fvalid ? e[a] * sc : 0.f, (uint32_t)((j0 + h + 2 * a) * A.Fs + f) * 4u,
                  (uint32_t)i * A.JP * A.Fs * 4u);
-        bstore(lzs, M + __builtin_amdgcn_logf(Z) * 0.69314718f, (h == 0 && wv == 0 && fvalid) ? (uint32_t)f * 4u : kNoStore,
-               (uint32_t)i * A.Fs * 4u);
       }
       float c[CP];
 #pragma unroll
@@ -1629,7 +1631,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   const uint32_t wvo = (uint32_t)(((tbase * 32 + r) * DIN + (DIN >= 16 ? 8 * h : 0)) * 2);
   const uint32_t bvo = (uint32_t)((tbase * 32 + r) * 8);
   const __amdgpu_buffer_rsrc_t crs = make_rsrc(A.cst, A.cst ? (size_t)A.in_n * A.JP * A.Fs * 4 : 0);
-  const __amdgpu_buffer_rsrc_t lzs = make_rsrc(A.lzst, A.cst ? (size_t)A.in_n * A.Fs * 4 : 0);
   // this lane's Vc fragments in registers (no LDS reads per capsule); LDS: the softmax
   // stats, then (din 32) two buffers of the shared x fragments (x_dma)
   float2* st = reinterpret_cast<float2*>(lds);
@@ -1773,8 +1774,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
           for (int a = 0; a < OWN; ++a)
             bstore(crs, fvalid ? e[a] * sc : 0.f, (uint32_t)((j0 + h + 2 * a) * A.Fs + f) * 4u,
                    (uint32_t)i * A.JP * A.Fs * 4u);
-          bstore(lzs, M + __builtin_amdgcn_logf(Z) * 0.69314718f,
-                 (h == 0 && wv == 0 && fvalid) ? (uint32_t)f * 4u : kNoStore, (uint32_t)i * A.Fs * 4u);
 #pragma unroll
           for (int a = 0; a < OWN; ++a) {
             float c0, c1;
@@ -1797,7 +1796,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
       if (more) {
         par ^= 1;
         logits(unext, par);
-        xl_wait<5 * TW + OWN + 1>();   // capsule i + 3's x has landed before the barrier
+        xl_wait<5 * TW + OWN>();   // capsule i + 3's x has landed before the barrier
         __syncthreads();
       }
       }
@@ -1838,8 +1837,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
       for (int a = 0; a < OWN; ++a)
         bstore(crs, fvalid ? e[a] * sc : 0.f, (uint32_t)((j0 + h + 2 * a) * A.Fs + f) * 4u,
                (uint32_t)i * A.JP * A.Fs * 4u);
-      bstore(lzs, M + __builtin_amdgcn_logf(Z) * 0.69314718f, (h == 0 && wv == 0 && fvalid) ? (uint32_t)f * 4u : kNoStore,
-             (uint32_t)i * A.Fs * 4u);
       float c[CP];
 #pragma unroll
       for (int a = 0; a < OWN; ++a) {
@@ -1861,7 +1858,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
       if (more) {   // capsule i + 1's logits and stats, then the one barrier
         par ^= 1;
         logits(unext, par);
-        if constexpr (XL) xl_wait<5 * TW + OWN + 1>();   // capsule i + 3's x has landed before the barrier
+        if constexpr (XL) xl_wait<5 * TW + OWN>();   // capsule i + 3's x has landed before the barrier
         __syncthreads();
       }
     };
@@ -1906,15 +1903,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
 // (Args32::cst), so no logit is recomputed:
 //   q_ij = <gs_j, u_ij>,  sigma_i = sum_j c_ij q_ij,  gL_ij = c_ij (q_ij - sigma_i),
 //   gVc_j (partial over the i-chunk) = sum_i gL_ij u_ij      -> slab
-//   stats[f][i] = (logZ_i, sigma_i)                            (for the gu pass)
+// The passes behind it (route_gux / route_gux16 / route_gw2 / route_gw3 / route_gw16s) take
+// c^r and gL^r and nothing else of a capsule's softmax: no (logZ, sigma) is kept, so the
+// capsule step loads only what the gradient uses (the couplings and the next operands).
 // gs^r rows live in each wave's private LDS slab in fragment order (as Vc in the
 // forward); sigma needs one cross-wave sum per input capsule (one barrier).
 struct Bwd32Args {
   const float* cst;   // c^r [in_n][JP][Fs]
-  const float* lz;    // logZ^r [in_n][Fs]
   const float* gs;    // gs^r [F][JD]
-  float* stats;       // [F][in_n][2]
-  float* glst;        // gL^r [in_n][JP][Fs] (laid out as c^r), for the gu pass
+  float* glst;        // gL^r [in_n][JP][Fs] (laid out as c^r), for the gx / gW passes
 };
 
 // the owned couplings j0 + 2a + h of one capsule i (p points at capsule j0 + h, frame f)
@@ -1936,10 +1933,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
   const int j0 = tbase * 32 / DOUT;
   const Rsrc3 rs{make_rsrc(A.Ws, A.ws_bytes), make_rsrc(A.bs, A.bs_bytes), make_rsrc(A.xs, A.xs_bytes)};
   if (DIN <= 16 && NW > 1 && wv >= NW / 2) __builtin_amdgcn_s_setprio(1);   // din 32: measured faster without
-  // logZ^r through a buffer descriptor: a 32-bit lane offset instead of a 64-bit
-  // pointer held across the capsule loop (which spilled, its reload's vmcnt(0) draining
-  // the operand prefetch)
-  const __amdgpu_buffer_rsrc_t lzr = make_rsrc(Bk.lz, (size_t)A.in_n * A.Fs * 4);
 
   f4* gsl = reinterpret_cast<f4*>(lds) + (size_t)tbase * 4 * 64;   // wave's slab, from the SGPR tbase = wv * TW
   float* st = lds + (size_t)NW * TW * 4 * 64 * 4;
@@ -1983,7 +1976,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
 #pragma unroll
   for (int t = 0; t < TW; ++t) acc[t] = f16v{};
   const float* crow = Bk.cst + (size_t)(j0 + h) * A.Fs + fc;
-  const __amdgpu_buffer_rsrc_t sts = make_rsrc(Bk.stats, (size_t)A.F * A.in_n * 8);
   const size_t cstep = (size_t)A.JP * A.Fs;   // next capsule i
   int par = 0;
   if (i0 < i1) {
@@ -1994,7 +1986,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
     if constexpr (XJ) {   // x of capsules i0, i0 + 1 before the first pose
       x_dma(xs_b, A.xplane_b, xsrc(i0), wv, xbuf(i0));
       x_dma(xs_b, A.xplane_b, xsrc(i0 + 1), wv, xbuf(i0 + 1));
-      xl_wait();
+      xl_wait_all();
       __syncthreads();
     }
     for (int i = i0; i < i1; ++i) {
@@ -2046,14 +2038,16 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         dots(TW - 1);
       }
       } else {
+      // this capsule's couplings ahead of the next capsule's W / bias loads (vmcnt counts in
+      // order: their wait then leaves those 5 per tile in flight); OWN registers held
+      // across the pose, whose MFMAs hide the latency
+      load_c<OWN>(crow + (size_t)i * cstep, A.Fs, cc);
+      __builtin_amdgcn_sched_barrier(0);
       const int in = min(i + 1, i1 - 1);
       pose_prog<DIN, TW, XJ, XJ>(fr, ones, u, rs, wvo, bvo,
                                  x_voff<DIN>(in, A.N, A.lpad, A.T, A.F, f, ftt, fvalid, h, A.zero_off), h,
                                  A.wplane_b, A.xplane_b, A.zero_off, (uint32_t)in * A.JDp * DIN * 2,
                                  (uint32_t)in * A.JDp * 8, xbuf(i) + lane_asm() * 16);
-      // this capsule's couplings: the pose MFMAs in flight hide their latency (no
-      // registers held across capsules)
-      load_c<OWN>(crow + (size_t)i * cstep, A.Fs, cc);
 #pragma unroll
       for (int t = 0; t < TW; ++t)
 #pragma unroll
@@ -2085,7 +2079,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         const int sr = lid & 31, shf = lid >> 5;
         float* slot = st + par * NW * 32;
         if (shf == 0) slot[wvu * 32 + sr] = S;
-        if constexpr (XJ) xl_wait();   // x of capsule i + 1 lands before the barrier that publishes it
+        // x of capsule i + 1 (DMA'd after the last barrier) lands before this one; the last
+        // capsule's gL stores, this capsule's couplings and the next capsule's W / bias
+        // loads (5 per tile) issued since may stay in flight (scripts/dbg/check_xl_wait4.py)
+        if constexpr (XJ) xl_wait<OWN + OWN + 5 * TW>();
         __syncthreads();
         if constexpr (XJ) x_dma(xs_b, A.xplane_b, xsrc(i + 2), wv, xbuf(i + 2));   // into capsule i's buffer
         constexpr int HW = NW / 2;
@@ -2097,17 +2094,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         S = s0 + s1;
         par ^= 1;
       }
-      // logZ of capsule i before the next capsule's operand loads: waiting for it at its
-      // store then leaves those (younger) loads in flight
-      const float lzv =
-          __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(lzr, (uint32_t)fc * 4u, (uint32_t)i * A.Fs * 4u, 0));
       __builtin_amdgcn_sched_barrier(0);
-      {
-        // (logZ, sigma) of frame f, capsule i: branch-free (wave 0, half 0, valid frames)
-        __builtin_amdgcn_raw_buffer_store_b64(
-            (unsigned __attribute__((ext_vector_type(2)))){__float_as_uint(lzv), __float_as_uint(S)}, sts,
-            (wv == 0 && h == 0 && fvalid) ? (uint32_t)(f * A.in_n) * 8u : kNoStore, (uint32_t)i * 8u, 0);
-      }
       // gL of the owned capsules (stored for the gu pass), then all-gather over the lane halves
       float gown[OWN];
 #pragma unroll
@@ -2162,7 +2149,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
 
 // Backward pass r >= 1, software-pipelined as route_fwd32p_kernel: capsule i + 1's
 // pose tiles run on the matrix cores while the VALU finishes capsule i (sigma over all
-// waves from behind last iteration's barrier, the stats / gL stores, gVc += gL u).
+// waves from behind last iteration's barrier, the gL stores, gVc += gL u).
 template <int DIN, int DOUT, int NW, int TW>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesPerEU))) void route_bwd32p_kernel(
     Args32 A, Bwd32Args Bk) {
@@ -2213,7 +2200,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
 #pragma unroll
   for (int t = 0; t < TW; ++t) acc[t] = f16v{};
   const float* crow = Bk.cst + (size_t)(j0 + h) * A.Fs + fc;
-  const __amdgpu_buffer_rsrc_t sts = make_rsrc(Bk.stats, (size_t)A.F * A.in_n * 8);
   const size_t cstep = (size_t)A.JP * A.Fs;
   if (i0 < i1) {
     Frags32<DIN, TW> fr;
@@ -2270,7 +2256,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
       if constexpr (DIN == 32) {
       const bool more = i + 1 < i1;
       x_dma(xs_b, A.xplane_b, xsrc(i + 3), wv, xbuf(i + 3));   // into the buffer capsule i + 1's x left
-      const float lzv = Bk.lz[(size_t)i * A.Fs + fc];
       load_c<OWN>(crow + (size_t)min(i + 1, i1 - 1) * cstep, A.Fs, cnext);
       constexpr int HW = NW / 2;
       float sv[HW];
@@ -2296,9 +2281,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
           float s0, s1;
           xpair32(sh, s0, s1);
           const float Sg = s0 + s1;
-          __builtin_amdgcn_raw_buffer_store_b64(
-              (unsigned __attribute__((ext_vector_type(2)))){__float_as_uint(lzv), __float_as_uint(Sg)}, sts,
-              (wv == 0 && h == 0 && fvalid) ? (uint32_t)(f * A.in_n) * 8u : kNoStore, (uint32_t)i * 8u, 0);
           float gown[OWN];
 #pragma unroll
           for (int a = 0; a < OWN; ++a) gown[a] = ccur[a] * (Q[a] - Sg);
@@ -2327,7 +2309,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
       if (more) {
         par ^= 1;
         dots(unext, cnext, par);
-        xl_wait<1 + OWN + 5 * TW + 1 + OWN>();   // capsule i + 3's x has landed
+        xl_wait<OWN + 5 * TW + OWN>();   // capsule i + 3's x has landed
         __syncthreads();
       }
       }
@@ -2337,9 +2319,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
       const bool more = i + 1 < i1;
       if constexpr (XL)   // x of capsule i + 3 into the buffer capsule i + 1's x left
         x_dma(xs_b, A.xplane_b, xsrc(i + 3), wv, xbuf(i + 3));
-      // logZ of capsule i before the next capsule's loads: waiting for it at its store
-      // then leaves those (younger) loads in flight
-      const float lzv = Bk.lz[(size_t)i * A.Fs + fc];
       // the next capsules' loads and pose run unconditionally (the chunk's last capsule
       // re-reads itself, its pose unused): with a branch around them the compiler cannot
       // count the loads in flight and waits for all of them at the stores below
@@ -2351,7 +2330,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
                                A.xplane_b, A.zero_off, (uint32_t)in * A.JDp * DIN * 2, (uint32_t)in * A.JDp * 8,
                                xbuf(i + 2) + lane * 16);
       }
-      // finish capsule i: sigma over all waves, stats, gL, gVc += gL u
+      // finish capsule i: sigma over all waves, gL, gVc += gL u
       float S;
       {
         constexpr int HW = NW / 2;
@@ -2363,9 +2342,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
         xpair32(sh, s0, s1);
         S = s0 + s1;
       }
-      __builtin_amdgcn_raw_buffer_store_b64(
-          (unsigned __attribute__((ext_vector_type(2)))){__float_as_uint(lzv), __float_as_uint(S)}, sts,
-          (wv == 0 && h == 0 && fvalid) ? (uint32_t)(f * A.in_n) * 8u : kNoStore, (uint32_t)i * 8u, 0);
       float gown[OWN];
 #pragma unroll
       for (int a = 0; a < OWN; ++a) gown[a] = ccur[a] * (Q[a] - S);
@@ -2395,7 +2371,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
       if (more) {
         par ^= 1;
         dots(unext, cnext, par);
-        if constexpr (XL) xl_wait<1 + OWN + 5 * TW + 1 + OWN>();   // capsule i + 3's x has landed
+        if constexpr (XL) xl_wait<OWN + 5 * TW + OWN>();   // capsule i + 3's x has landed
         __syncthreads();
       }
     };
@@ -2716,7 +2692,6 @@ static Args32 make_args32(const Fwd32Plan& p, const DrGeom& g, const void* plane
   a.bsum = reinterpret_cast<const float*>(scratch);
   a.slab = fwd32_slab(p, scratch);
   a.cst = nullptr;
-  a.lzst = nullptr;
   a.JP = p.JDp / g.dout;
   a.Fs = fwd32_frame_stride(g.F());
   a.bal_G = p.bal_G;
@@ -2792,11 +2767,10 @@ int fwd32_first_full(const Fwd32Plan& p, const DrGeom& g, const void* planes, vo
 }
 
 int fwd32_pass(const Fwd32Plan& p, const DrGeom& g, bool first, const void* planes, void* scratch, const float* vc,
-               float* cst, float* lzst, hipStream_t st) {
+               float* cst, hipStream_t st) {
   Args32 a = make_args32(p, g, planes, scratch);
   a.vc = vc;
   a.cst = first ? nullptr : cst;
-  a.lzst = first ? nullptr : lzst;
   SRF_REQUIRE(2 * p.xplane * 2 < (1ull << 31) && p.ws_w < (1ull << 31), "fwd32: operand planes exceed 2 GiB");
   return dispatch_row(g, "fwd32", [&](auto di, auto dout) {
     if (first) {
@@ -2815,10 +2789,10 @@ int fwd32_pass(const Fwd32Plan& p, const DrGeom& g, bool first, const void* plan
 }
 
 int bwd32_pass(const Fwd32Plan& p, const DrGeom& g, const void* planes, void* scratch, const float* cst,
-               const float* lz, const float* gs, float* stats, float* glst, hipStream_t st) {
+               const float* gs, float* glst, hipStream_t st) {
   Args32 a = make_args32(p, g, planes, scratch);
   a.mask_first = 0;   // the mask is in the stored couplings; the backward kernels do not read it
-  const Bwd32Args b{cst, lz, gs, stats, glst};
+  const Bwd32Args b{cst, gs, glst};
   return dispatch_row(g, "bwd32", [&](auto di, auto dout) {
     return dispatch_tiles<di>(p, [&](auto nw, auto tw) {
       return launch_rpass<nw, tw>(p, "route_bwd32", route_bwd32p_kernel<di, dout, (nw > 1 ? nw : 2), (tw <= 2 ? tw : 2)>,
