@@ -718,6 +718,48 @@ int srf_fbank_deltas(const float* statics, const int* n_frames, int B, int Ts, i
                      const float* mean, const float* stdev, int cmvn_rows, float* feats, int To, int o0, void* stream);
 int srf_fbank_stats(const float* feats, const int* n_frames, int B, int T, int D, double* sums, void* stream);
 
+/* ---- Resampler: audio at any rate to another (16 kHz for the front end) ------
+ * Kaldi's LinearResample as ResampleWaveform configures it (what compute-fbank-feats applies
+ * to input whose rate is not --sample-frequency); DESIGN.md section 19 has the definition.
+ * Rates fin, fout are integers in [4000, 192000]; g = gcd, iu = fin / g, ou = fout / g;
+ * cutoff fc = 0.99 * 0.5 * min(fin, fout), half width ww = 6 / (2 fc) seconds.  Output o has
+ * phase p = o mod ou and unit u = o div ou; with t = p / fout, first[p] = ceil((t - ww) fin),
+ * w[p][j] = win(d) filt(d) / fin at d = (first[p] + j) / fin - t, win(d) = (1 + cos(2 pi fc
+ * d / 6)) / 2 inside |d| < ww (else 0), filt(d) = sin(2 pi fc d) / (pi d) (2 fc at 0); taps
+ * is the longest row, shorter rows end in zeros.  y[o] = sum_{j < taps} w[p][j] x[first[p] +
+ * u iu + j] with x zero outside [0, n), summed in fp32 in the order of j, one fma per tap.
+ * n input samples give ceil(n ou / iu) outputs (srf_resample_num_out, 64-bit arithmetic).
+ * fin == fout is the exact copy: one tap of weight 1.
+ *
+ * tables: one block for a bank of up to SRF_RESAMPLE_MAX_RATES input rates and one output
+ * rate, srf_resample_table_floats floats (0 and a message if refused), filled on the host
+ * by srf_resample_tables in double, rounded once, and copied to the device by the caller.
+ * Layout (every entry a float): [0] the number of rates, [1] fout, [2 .. 7] zero; rate r has
+ * the 8 floats at SRF_RESAMPLE_HEADER + 8 r = [iu, ou, taps, offset of first, offset of w,
+ * fin, 0, 0]; from SRF_RESAMPLE_HEADER + 8 SRF_RESAMPLE_MAX_RATES on, per rate first[ou] and
+ * w[ou][taps].  Refused: a rate outside the range, more than SRF_RESAMPLE_MAX_RATES rates, a
+ * bank whose weights exceed 2^20 floats.
+ *
+ * srf_resample: outputs [o0, o1) of every row, one launch.  samples [B][stride], int16
+ * (is_int16 = 1) or float32, of which columns [0, width) hold the global samples s0 .. s0 +
+ * width - 1; n_samples [B] (device) the rows' lengths; choice [B] (device) a row's index
+ * into the bank, clamped to it, or NULL: 0 for every row; rates_in [n_rates] (host) and
+ * rate_out are the rates the block was built for.  n_b = min(max(n_samples[b], 0), n_limit),
+ * n_limit <= s0 + width the samples that have arrived.  out [B][stride_out], column c =
+ * output q0 + c: outputs o < num_out(n_b) get y[o] with inputs at indices >= n_b read as
+ * zero, outputs num_out(n_b) <= o < o1 get 0; n_out [B] (device, or NULL) receives
+ * num_out(n_b), capped at 2^31 - 1, from the same launch.  Refused before any launch: n_limit beyond the
+ * buffer, outputs outside the output buffer, o1 > 2^31 - 2049, and, for any rate of the
+ * bank, a first tap of output o0 that lies below s0 > 0.  No workspace, no atomics. */
+#define SRF_RESAMPLE_MAX_RATES 8
+#define SRF_RESAMPLE_HEADER 8
+size_t srf_resample_table_floats(const int* rates_in, int n_rates, int rate_out);
+int srf_resample_tables(const int* rates_in, int n_rates, int rate_out, float* tables, size_t n_floats);
+size_t srf_resample_num_out(size_t n, int rate_in, int rate_out);
+int srf_resample(const void* samples, int is_int16, const int* n_samples, const int* choice, const float* tables,
+                 const int* rates_in, int n_rates, int rate_out, int B, int stride, int width, int s0, int n_limit,
+                 int o0, int o1, float* out, int stride_out, int q0, int* n_out, void* stream);
+
 /* ---- Fused Adam over one flat parameter buffer ----------------------------
  * Replaces the Keras Adam apply of trainer_sr.py:71 / train_helper.py:60-70:
  * m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= alpha m / (sqrt(v) + eps),

@@ -105,6 +105,14 @@ def check_audio_chunk(n, max_chunk):
                          f'(max_chunk = {max_chunk}), got {n}')
 
 
+def resampled_chunk_bound(max_chunk, iu, ou, hold):
+    """Most input samples one ``push_audio`` call takes through a resampler of ratio iu : ou
+    that holds back at most ``hold`` outputs: n inputs release at most ceil(n ou / iu) + hold
+    outputs (what n_out grows by, plus what the end of the streams lets go), which one
+    ``FbankStream.push`` of audio_chunk_bound(max_chunk) samples must take."""
+    return max(0, audio_chunk_bound(max_chunk) - int(hold)) * int(iu) // int(ou)
+
+
 class StreamOut:
     """What one ``push`` / ``finish`` emitted: output frames [t0, t0 + m) of every
     stream.  ``logits`` [B, m, C] (device); ``labels``: per stream, the greedy labels
@@ -152,9 +160,17 @@ class StreamingRouter:
     end-of-stream flush included; more raises ``ValueError``.  ``finish()`` flushes the front
     end first, ``reset()`` resets it.  ``lookahead_audio_ms`` is what the audio side adds to
     the model's lookahead: 4 feature frames (the delta-delta's reach, 40 ms) plus the
-    frame's own 25 ms."""
+    frame's own 25 ms.
 
-    def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None, lm=None, frontend=None):
+    With ``resampler`` as well (a single-rate ``srf_amd.resample.Resampler`` whose output rate
+    is 16 kHz) ``push_audio`` takes samples at the resampler's input rate, ``ended`` in input
+    samples, and feeds ``resample.ResampleStream`` -> ``FbankStream`` -> ``push``.  One call
+    then takes at most ``audio_bound`` input samples, the largest chunk whose outputs cannot
+    exceed audio_chunk_bound(max_chunk); ``lookahead_audio_ms`` grows by the filter's half
+    width, 6000 / (0.99 min(fin, fout)) ms."""
+
+    def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None, lm=None, frontend=None,
+                 resampler=None):
         if model.caps_type == 'einsum':
             raise ValueError('the einsum variant cannot stream: its positional encoding needs the absolute frame '
                              'index, which srf_primary_caps_fwd_ex does not take')
@@ -179,6 +195,22 @@ class StreamingRouter:
             if audio_chunk_bound(max_chunk) < 1:
                 raise ValueError(f'a front end needs max_chunk >= 12 input frames, got {max_chunk}')
             self._fe = fbank.FbankStream(frontend, int(n_streams), audio_chunk_bound(max_chunk))
+        self._rs = None
+        if resampler is not None:
+            from . import resample
+            if frontend is None:
+                raise ValueError('a resampler feeds the front end: it comes with a frontend')
+            if resampler.rate_out != 16000:
+                raise ValueError(f'the front end reads 16 kHz audio, the resampler makes {resampler.rate_out} Hz')
+            f = resampler.filters[0]
+            hold = resample.stream_hold(f['first'], f['taps'], f['iu'])
+            self.audio_bound = resampled_chunk_bound(max_chunk, f['iu'], f['ou'], hold)
+            if self.audio_bound < 1:
+                raise ValueError(f'max_chunk = {max_chunk} leaves no room for a chunk of resampled audio')
+            self._rs = resample.ResampleStream(resampler, int(n_streams), self.audio_bound)
+            self._audio_bound_why = (f'(160 * (max_chunk - 8) - {hold}) * {f["iu"]} // {f["ou"]} = {self.audio_bound} '
+                                     f'samples at {resampler.rates_in[0]} Hz')
+            self.lookahead_audio_ms += 6000.0 / (0.99 * min(resampler.rates_in[0], resampler.rate_out))
         self.blank = model.class_n - 1
         self.device = model.flat_params.device
         # the routing buffers' timeline: the last layer's next frame D sits at local
@@ -236,6 +268,8 @@ class StreamingRouter:
         self._beam_best = None  # (labels, scores) of the frames pushed so far, once fetched
         if self._fe is not None:
             self._fe.reset()
+        if self._rs is not None:
+            self._rs.reset()
         self._held = None       # final feature frames that wait for their group of 4
         self._frame_len = [None] * self.B   # frame counts of the streams whose audio ended
 
@@ -374,10 +408,26 @@ class StreamingRouter:
             raise ValueError('this router takes features only: build it with a frontend')
         if self._finished:
             raise ValueError('push_audio after finish(): call reset() to start new utterances')
+        if self._rs is not None:
+            if samples.dim() == 2 and samples.shape[1] > self.audio_bound:
+                raise ValueError(f'push_audio takes at most {self._audio_bound_why} per call '
+                                 f'(max_chunk = {self.max_chunk}), got {samples.shape[1]}')
+            with torch.no_grad():
+                return self._push_frames(self._fe.push(*self._resampled(self._rs.push(samples, ended))), False)
         if samples.dim() == 2:
             check_audio_chunk(samples.shape[1], self.max_chunk)
         with torch.no_grad():
             return self._push_frames(self._fe.push(samples, ended), False)
+
+    def _resampled(self, y):
+        """(y, ended) for ``FbankStream.push``: the 16 kHz samples the resampler made final, with
+        the output sample counts of the streams whose last output is among them."""
+        rs, fe = self._rs, self._fe
+        ended = [-1] * self.B
+        for b, e in enumerate(rs.lengths):
+            if e is not None and fe.lengths[b] is None and rs.rs.n_out(e) <= fe.pushed + y.shape[1]:
+                ended[b] = rs.rs.n_out(e)
+        return y, (ended if any(e >= 0 for e in ended) else None)
 
     def _push_frames(self, new, flush):
         """Final feature frames to ``push``, in groups of 4 (``flush``: all of them, zero
@@ -410,19 +460,22 @@ class StreamingRouter:
         ``StreamOut`` covers both steps."""
         if self._finished:
             raise ValueError('finish() was already called: call reset() to start new utterances')
-        first = None
+        first = []
         if self._fe is not None:
             with torch.no_grad():
-                first = self._push_frames(self._fe.finish(), True)
+                if self._rs is not None:
+                    first.append(self._push_frames(self._fe.push(*self._resampled(self._rs.finish())), False))
+                first.append(self._push_frames(self._fe.finish(), True))
         self._check_beam_room(0, True)
         with torch.no_grad():
             out = self._step(None, True)
         self._finished = True
-        if first is not None and first.logits.shape[1]:
+        parts = [o for o in first if o.logits.shape[1]] + [out]
+        if len(parts) > 1:
             self._fetch_labels()
-            both = StreamOut(self, first.t0, torch.cat([first.logits, out.logits], dim=1))
-            both._labels = [a + b for a, b in zip(first._labels, out._labels)]
-            both._frames = [a + b for a, b in zip(first._frames, out._frames)]
+            both = StreamOut(self, parts[0].t0, torch.cat([o.logits for o in parts], dim=1))
+            both._labels = [sum((o._labels[b] for o in parts), []) for b in range(self.B)]
+            both._frames = [sum((o._frames[b] for o in parts), []) for b in range(self.B)]
             return both
         return out
 
