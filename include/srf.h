@@ -51,6 +51,20 @@ int srf_route_dr_auto_chunks(int B, int T, int N, int din, int lpad, int rpad, i
  * other shapes are an error. */
 int srf_route_dr_split_table(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks,
                              int* info, int* table, int capacity);
+/* A balanced plan runs one persistent workgroup per span of srf_route_dr_split_table.
+ * on != 0: the spans are placed on the XCDs by their capsule phase, so the workgroups
+ * of an XCD read neighbouring W slabs and share them in its L2; 0: block b runs
+ * workgroup b.  Process-global, read when a pass is launched (a captured graph keeps
+ * what it was captured with); the default is the library's SRF_DR_BAL_XCD.  A
+ * permutation of which block runs which span: every result is bit for bit the same
+ * but g_emb, whose float atomics reorder.  Chunked plans are not affected. */
+int srf_route_dr_set_bal_placement(int on);
+/* Host only: the placement under the current setting.  block_to_wg receives, for up to
+ * `capacity` blocks, the workgroup (row `workgroup` of the split table) that block b of
+ * the pass grid runs.  Returns the number of workgroups G (which may exceed capacity),
+ * 0 for a chunked plan, and a negative error where srf_route_dr_split_table does. */
+int srf_route_dr_split_placement(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks,
+                                 int* block_to_wg, int capacity);
 size_t srf_route_dr_saved_floats(int B, int T, int J, int dout, int iters);
 size_t srf_route_dr_fwd_workspace(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int iters,
                                   int n_chunks);

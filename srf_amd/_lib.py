@@ -53,6 +53,8 @@ _SIGNATURES = {
     'srf_set_fault_flag': (_c_int, [_vp]),
     'srf_route_dr_auto_chunks': (_c_int, [_c_int] * 8),
     'srf_route_dr_split_table': (_c_int, [_c_int] * 9 + [_vp, _vp, _c_int]),
+    'srf_route_dr_set_bal_placement': (_c_int, [_c_int]),
+    'srf_route_dr_split_placement': (_c_int, [_c_int] * 9 + [_vp, _c_int]),
     'srf_route_dr_saved_floats': (_c_size, [_c_int] * 5),
     'srf_route_dr_fwd_workspace': (_c_size, [_c_int] * 10),
     'srf_route_dr_bwd_workspace': (_c_size, [_c_int] * 10),

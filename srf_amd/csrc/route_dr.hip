@@ -2774,6 +2774,26 @@ int srf_route_dr_split_table(int B, int T, int N, int din, int lpad, int rpad, i
   return n;
 }
 
+int srf_route_dr_set_bal_placement(int on) {
+  srf::fwd32_set_bal_placement(on != 0);
+  return SRF_OK;
+}
+
+int srf_route_dr_split_placement(int B, int T, int N, int din, int lpad, int rpad, int J, int dout, int n_chunks,
+                                 int* block_to_wg, int capacity) {
+  const bool shape_ok = B > 0 && T > 0 && N > 0 && lpad >= 0 && rpad >= 0;
+  const DrPlan plan = shape_ok ? query(B, T, N, din, lpad, rpad, J, dout, 1, n_chunks) : DrPlan{};
+  SRF_REQUIRE(shape_ok && plan.fwd32, "split_placement: not a 32x32-pass shape");
+  SRF_REQUIRE(n_chunks == 0 || plan_arg_ok(plan, n_chunks), "split_placement: bad plan argument %d", n_chunks);
+  SRF_REQUIRE(capacity >= 0 && (block_to_wg != nullptr || capacity == 0), "split_placement: null argument");
+  const srf::Fwd32Plan& p = plan.p32;
+  if (p.bal_G <= 0) return 0;
+  int d, inv;   // as make_args32 passes them to the pass kernels
+  srf::bal_place_params(p.bal_G, p.n_ftiles, srf::fwd32_bal_placement(), &d, &inv);
+  for (int b = 0; b < p.bal_G && b < capacity; ++b) block_to_wg[b] = srf::bal_place(b, p.bal_G, d, inv);
+  return p.bal_G;
+}
+
 size_t srf_route_dr_saved_floats(int B, int T, int J, int dout, int iters) {
   return (size_t)2 * iters * B * T * J * dout;
 }

@@ -39,6 +39,42 @@ __host__ __device__ inline int bal_owner(int u, int U, int G) {
 __host__ __device__ inline int bal_tile_slots(int ft, int in_n, int U, int G) {
   return bal_owner((ft + 1) * in_n - 1, U, G) - bal_owner(ft * in_n, U, G) + 1;
 }
+// Placement of the balanced spans on the XCDs.  Workgroup w walks capsule (p_w + k) % in_n
+// at its step k, p_w = bal_first(w) % in_n, so the distance between two workgroups'
+// capsules lasts for the whole pass; p_w / in_n is, up to the floor, (w * n_ft % G) / G
+// (U / (G * in_n) = n_ft / G).  The dispatcher deals blocks round-robin over the 8 XCDs:
+// XCD x runs blocks x, x + 8, ...  With block b = workgroup b an XCD's workgroups are
+// spread over all of W at every step; bal_place instead ranks the blocks XCD-major and
+// hands rank r the workgroup of the r-th smallest phase, so an XCD's workgroups read
+// neighbouring W slabs and share them in its L2.  With d = gcd(n_ft, G), G' = G / d and
+// inv = (n_ft / d)^-1 mod G' (bal_place_params), the phases are the multiples of d / G,
+// each held by the d workgroups w0 + j * G'.  d = 0 is the identity (placement off, or
+// G <= 8: one block per XCD).  A permutation of who runs which span: no segment, slab
+// slot or sum depends on it.  G * G < 2^32 (G <= U, U * (G + 1) < 2^31).
+__host__ __device__ inline int bal_place(int b, int G, int d, int inv) {
+  if (d == 0) return b;
+  const uint32_t x = (uint32_t)b & 7u, k = (uint32_t)b >> 3, q = (uint32_t)G >> 3, rem = (uint32_t)G & 7u;
+  const uint32_t r = x * q + (x < rem ? x : rem) + k;
+  const uint32_t Gp = (uint32_t)G / (uint32_t)d;
+  return (int)((r / (uint32_t)d) * (uint32_t)inv % Gp + (r % (uint32_t)d) * Gp);
+}
+// d and inv of bal_place for G workgroups over n_ft frame tiles (d = 0: identity)
+inline void bal_place_params(int G, int n_ft, bool on, int* d, int* inv) {
+  *d = 0, *inv = 0;
+  if (!on || G <= 8 || n_ft <= 0) return;
+  int a = n_ft, b = G;
+  while (b) { const int t = a % b; a = b, b = t; }
+  const int Gp = G / a, m = (n_ft / a) % Gp;
+  int v = 0;   // Gp is small (<= G): search the inverse; Gp = 1 gives 0
+  for (int c = 0; c < Gp; ++c)
+    if ((long long)c * m % Gp == 1 % Gp) { v = c; break; }
+  *d = a, *inv = v;
+}
+// Process-global switch of the placement (srf_route_dr_set_bal_placement); the default
+// is the compile-time SRF_DR_BAL_XCD.  Read when a pass is launched (or captured).
+void fwd32_set_bal_placement(bool on);
+bool fwd32_bal_placement();
+
 // The plan argument `n_chunks` of every entry point selects the split: 0 = the cost
 // model's choice, 1 .. in_n = that many uniform i-chunks, kBalFlag | G = the balanced
 // split over G workgroups (G = 0: as many as are resident).  srf_route_dr_auto_chunks

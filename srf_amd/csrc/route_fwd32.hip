@@ -67,6 +67,13 @@
 #define SRF_PREP32_ONEPASS 1
 #endif
 
+// SRF_DR_BAL_XCD: 1 = the balanced passes place their spans on the XCDs by capsule phase
+// (bal_place, route_fwd32.h); 0 = block b runs workgroup b.  The default of the runtime
+// switch srf_route_dr_set_bal_placement.
+#ifndef SRF_DR_BAL_XCD
+#define SRF_DR_BAL_XCD 1
+#endif
+
 namespace {
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
@@ -938,8 +945,9 @@ struct Args32 {
   float* cst;
   int JP, Fs;
   // balanced split of the r >= 1 passes (bal_G > 0): workgroup w walks the units
-  // [bal_first(w), bal_first(w + 1)) of bal_U = n_ftiles * in_n (route_fwd32.h)
-  int bal_G, bal_U;
+  // [bal_first(w), bal_first(w + 1)) of bal_U = n_ftiles * in_n (route_fwd32.h); block b
+  // is workgroup bal_place(b, bal_G, bal_d, bal_inv)
+  int bal_G, bal_U, bal_d, bal_inv;
 };
 
 // One segment of a pass workgroup: input capsules [i0, i1) of frame tile ft, partial sum
@@ -964,6 +972,14 @@ __device__ __forceinline__ const __attribute__((address_space(4))) T* kernarg_re
   return (const __attribute__((address_space(4))) T*)(p + off);
 }
 
+// The logical workgroup of this block under a balanced plan (bal_place).  Re-derived from
+// the kernel arguments wherever it is needed, like they are, instead of held in an SGPR.
+template <class ArgsT>
+__device__ __forceinline__ int bal_wg(const ArgsT& A) {
+  return __builtin_amdgcn_readfirstlane(srf::bal_place((int)blockIdx.x, A.bal_G, A.bal_d, A.bal_inv));
+}
+
+// bid: the block of a chunked plan, the logical workgroup of a balanced one
 template <class ArgsT>
 __device__ __forceinline__ Seg32 seg32_at(const ArgsT& A, int bid, int u, int u1) {
   int ft, i0, i1, slot;
@@ -990,18 +1006,18 @@ __device__ __forceinline__ Seg32 seg32_at(const ArgsT& A, int bid, int u, int u1
 struct SegWalk {
   int u;   // the next unit of a balanced span (the one value carried from segment to segment)
   __device__ __forceinline__ SegWalk(const Args32& A) : u(0) {
-    if (A.bal_G > 0) u = __builtin_amdgcn_readfirstlane(srf::bal_first((int)blockIdx.x, A.bal_U, A.bal_G));
+    if (A.bal_G > 0) u = __builtin_amdgcn_readfirstlane(srf::bal_first(bal_wg(A), A.bal_U, A.bal_G));
   }
   __device__ __forceinline__ Seg32 seg() const {
     const auto* K = kernarg_reload<Args32>(0);
-    const int bid = blockIdx.x;
+    const int bid = K->bal_G > 0 ? bal_wg(*K) : (int)blockIdx.x;
     return seg32_at(*K, bid, u, K->bal_G > 0 ? srf::bal_first(bid + 1, K->bal_U, K->bal_G) : 0);
   }
   __device__ __forceinline__ bool next(const Seg32& sg) {
     const auto* K = kernarg_reload<Args32>(0);
     if (K->bal_G <= 0) return false;
     u += sg.i1 - sg.i0;
-    if (u >= __builtin_amdgcn_readfirstlane(srf::bal_first((int)blockIdx.x + 1, K->bal_U, K->bal_G))) return false;
+    if (u >= __builtin_amdgcn_readfirstlane(srf::bal_first(bal_wg(*K) + 1, K->bal_U, K->bal_G))) return false;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     return true;
@@ -2414,6 +2430,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(kWavesP
 
 namespace srf {
 
+static bool g_bal_placement = SRF_DR_BAL_XCD != 0;
+void fwd32_set_bal_placement(bool on) { g_bal_placement = on; }
+bool fwd32_bal_placement() { return g_bal_placement; }
+
 bool fwd32_supported(int din, int dout, int J) {
   return (din == 8 || din == 16 || din == 32) && (dout == 8 || dout == 16 || dout == 32) && din <= dout &&
          J * dout <= 32 * kTW * kMaxNW && (J * dout) % 8 == 0;
@@ -2696,6 +2716,7 @@ static Args32 make_args32(const Fwd32Plan& p, const DrGeom& g, const void* plane
   a.Fs = fwd32_frame_stride(g.F());
   a.bal_G = p.bal_G;
   a.bal_U = p.bal_U;
+  if (p.bal_G > 0) srf::bal_place_params(p.bal_G, p.n_ftiles, fwd32_bal_placement(), &a.bal_d, &a.bal_inv);
   return a;
 }
 
