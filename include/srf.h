@@ -684,8 +684,9 @@ int srf_stream_advance_n(const srf_stream_buf* bufs, int n_bufs, int B, void* st
 /* ---- Waveform front end: 16 kHz samples to 123-d fbank features -------------
  * Replaces the Kaldi step of egs/script/fbank123.sh (compute-fbank-feats --num-mel-bins=40
  * --sample-frequency=16000 --use-log-fbank=True --use-energy=True, add-deltas, CMVN as
- * save_speech_data.py:163 applies it).  fp32 throughout; DESIGN.md section 18 has the
- * definitions.  Samples are in int16 scale, int16 (is_int16 = 1) or float32.
+ * save_speech_data.py:163 applies it; the online CMVN of a live stream is srf_cmvn_sliding
+ * below).  fp32 throughout; DESIGN.md section 18 has the definitions.  Samples are in int16
+ * scale, int16 (is_int16 = 1) or float32.
  *
  * Framing (snip-edges): T(n) = 0 for n < 400, else 1 + (n - 400) / 160 (srf_fbank_num_frames);
  * frame t is samples 160 t .. 160 t + 399 of its stream.
@@ -731,6 +732,37 @@ int srf_fbank_static(const void* samples, int is_int16, const int* n_samples, co
 int srf_fbank_deltas(const float* statics, const int* n_frames, int B, int Ts, int f0, int t_limit, int t0, int t1,
                      const float* mean, const float* stdev, int cmvn_rows, float* feats, int To, int o0, void* stream);
 int srf_fbank_stats(const float* feats, const int* n_frames, int B, int T, int D, double* sums, void* stream);
+
+/* ---- Online CMVN: sliding-window normalisation of feature rows ---------------
+ * What a live stream applies in place of the per-speaker CMVN above, whose statistics
+ * need the speaker's utterances in advance (Kaldi's OnlineCmvn in spirit; DESIGN.md
+ * section 20 is the definition).  For stream b, frame t < T_b = max(n_frames[b], 0) and
+ * dimension d, in fp64 with one rounding to fp32 at the end, W = window:
+ *   lo = max(0, t - W + 1), n = t - lo + 1, S1 = sum_{u = lo .. t} x[u], S2 = sum x[u]^2,
+ *   c = min(W - n, prior_count[b]) (0 without a prior),
+ *   m = (S1 + c mean_p) / (n + c), q = (S2 + c (std_p^2 + mean_p^2)) / (n + c),
+ *   y = (x[t] - m) / sqrt(max(q - m m, 1e-10)) with norm_vars, else y = x[t] - m.
+ * The prior: prior_rows = 0 (none), 1 (prior_mean, prior_std [D] and prior_count [1],
+ * shared) or B ([B][D] and [B]), doubles on the device.
+ *
+ * srf_cmvn_sliding: frames [t0, t1) of out [B][To][D], row r = frame o0 + r, from feats
+ * [B][rows][D], row r = frame f0 + r; rows of frames T_b <= t < t1 get zeros.  The sums
+ * are taken per tile of SRF_CMVN_TILE absolute frames: in ascending frame order over the
+ * window of the tile's first frame, then slid frame by frame, "- x[t - W]" before
+ * "+ x[t]".  A launch that starts inside a tile recomputes from the tile's first frame, so
+ * a frame's bits depend on its stream's frames and on t alone, not on t0, t1, f0, B or the
+ * chunking, and the input must hold the frames from
+ * max(0, t0 / SRF_CMVN_TILE * SRF_CMVN_TILE - W + 1) to t1 - 1; anything else is refused
+ * before the launch.  last (device, or NULL) [B][2 D + 1] doubles: a stream whose frame
+ * min(T_b, t1) - 1 lies in [t0, t1) gets [m | q | n + c] of that frame, what its last
+ * frame so far was normalised with (the speaker carry reads it); other streams' rows are
+ * left alone.  One launch, no workspace, no atomics, nothing read back. */
+#define SRF_CMVN_TILE 32
+#define SRF_CMVN_MAX_DIM 128
+#define SRF_CMVN_MAX_WINDOW 4096
+int srf_cmvn_sliding(const float* feats, const int* n_frames, int B, int rows, int D, int f0, int t0, int t1,
+                     const double* prior_mean, const double* prior_std, const double* prior_count, int prior_rows,
+                     int window, int norm_vars, float* out, int To, int o0, double* last, void* stream);
 
 /* ---- Resampler: audio at any rate to another (16 kHz for the front end) ------
  * Kaldi's LinearResample as ResampleWaveform configures it (what compute-fbank-feats applies

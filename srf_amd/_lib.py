@@ -171,7 +171,9 @@ _SIGNATURES = {
     'srf_fbank_static': (_c_int, [_vp, _c_int, _vp, _vp] + [_c_int] * 9 + [ctypes.c_float, ctypes.c_ulonglong, _vp, _vp]),
     'srf_fbank_deltas': (_c_int, [_vp, _vp] + [_c_int] * 6 + [_vp, _vp, _c_int, _vp, _c_int, _c_int, _vp]),
     'srf_fbank_stats': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
-    'srf_resample_table_floats': (_c_size, [_vp, _c_int, _c_int]),
+    'srf_cmvn_sliding': (_c_int, [_vp, _vp] + [_c_int] * 6 + [_vp, _vp, _vp] + [_c_int] * 3
+                         + [_vp, _c_int, _c_int, _vp, _vp]),
+    'srf_resample_table_floats':(_c_size, [_vp, _c_int, _c_int]),
     'srf_resample_tables': (_c_int, [_vp, _c_int, _c_int, _vp, _c_size]),
     'srf_resample_num_out': (_c_size, [_c_size, _c_int, _c_int]),
     'srf_resample': (_c_int, [_vp, _c_int, _vp, _vp, _vp, _vp] + [_c_int] * 9 + [_vp, _c_int, _c_int, _vp, _vp]),

@@ -160,7 +160,9 @@ class StreamingRouter:
     end-of-stream flush included; more raises ``ValueError``.  ``finish()`` flushes the front
     end first, ``reset()`` resets it.  ``lookahead_audio_ms`` is what the audio side adds to
     the model's lookahead: 4 feature frames (the delta-delta's reach, 40 ms) plus the
-    frame's own 25 ms.
+    frame's own 25 ms.  A front end whose CMVN is a ``fbank.SlidingCmvn`` normalises online
+    and adds nothing to that; ``reset(carry_cmvn=True)`` keeps what it learnt about each
+    stream's speaker as the prior of the next utterance.
 
     With ``resampler`` as well (a single-rate ``srf_amd.resample.Resampler`` whose output rate
     is 16 kHz) ``push_audio`` takes samples at the resampler's input rate, ``ended`` in input
@@ -247,8 +249,12 @@ class StreamingRouter:
         n = _lib.lib().srf_route_sdr_recur_workspace(self.B, in_n, J, D, self.model.route_iters)
         return torch.zeros(max(n, 16), device=self.device, dtype=torch.uint8)
 
-    def reset(self):
-        """Every stream back at its start."""
+    def reset(self, carry_cmvn=False):
+        """Every stream back at its start.  ``carry_cmvn``: a front end with a sliding CMVN
+        keeps what it learnt about each stream's speaker as the prior of the next utterance
+        (``fbank.FbankStream.reset(carry=True)``)."""
+        if carry_cmvn and self._fe is None:
+            raise ValueError('carry_cmvn needs a front end with a sliding CMVN')
         for t in self._emb + self._v:
             t.zero_()   # zero frames before the start: the window's padding and the SDR carry v_0 = 0
         self._tail.zero_()
@@ -267,7 +273,7 @@ class StreamingRouter:
             self._beam.reset()
         self._beam_best = None  # (labels, scores) of the frames pushed so far, once fetched
         if self._fe is not None:
-            self._fe.reset()
+            self._fe.reset(carry=carry_cmvn)
         if self._rs is not None:
             self._rs.reset()
         self._held = None       # final feature frames that wait for their group of 4
