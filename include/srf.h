@@ -633,6 +633,51 @@ int srf_ctc_beam_lm_best(const void* state, size_t state_bytes, int B, int C, in
 int srf_ctc_beam_lm_nbest(const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int N,
                           int max_len, int* labels, int* count, float* score, float* lm_score, int* n_hyp,
                           void* stream);
+/* srf_ctc_beam_cut / srf_ctc_beam_lm_cut: close a segment of some utterances (endpointing,
+ * below).  cut [B] (device): for every utterance with cut[b] >= 0, what best would return
+ * goes to labels [B][max_len] (labels at index max_len and beyond are not stored), count
+ * [B], log_prob / score [B] and, fused, lm_score [B]; then that utterance alone is put back
+ * to the reset state, header and beam entry 0 as reset leaves them (fused: state 0 and no
+ * bonus).  An utterance with cut[b] < 0 gets count[b] = -1 and is not touched otherwise.
+ * The host counter frames_pushed is not involved.
+ * With rest (else null, and logits, n_valid, n_rest may be null): cut[b] is the chunk frame
+ * of logits [B][n][C] that ended the segment, cut[b] < n; the frames after it, [cut[b] + 1,
+ * clamp(n_valid[b], 0, n)), are copied to the front of rest [B][n][C] and n_rest [B]
+ * receives their number (0 for an utterance without a cut): the push that opens the next
+ * segment, srf_ctc_beam_push_n taking no per-utterance first frame. */
+int srf_ctc_beam_cut(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, const int* cut,
+                     int max_len, int* labels, int* count, float* log_prob, const float* logits, const int* n_valid,
+                     int n, float* rest, int* n_rest, void* stream);
+int srf_ctc_beam_lm_cut(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, const int* cut,
+                        int max_len, int* labels, int* count, float* score, float* lm_score, const float* logits,
+                        const int* n_valid, int n, float* rest, int* n_rest, void* stream);
+
+/* ---- Endpointing (srf_amd/endpoint.py) ---------------
+ * Where an utterance ends, from the CTC logits alone.  Per stream the state is n (frames in
+ * the open segment), sil (trailing silence run), speech (a flag) and t (frames consumed
+ * since the reset, an int); for every consumed frame x [C], in order:
+ *   lp_blank = x[blank] - (max(x) + log(sum(exp(x - max(x)))))          (fp32)
+ *   is_sil   = lp_blank > log_thr,   is_sp = argmax(x) != blank  (lowest index on a tie)
+ *   n += 1;  sil = is_sil ? sil + 1 : 0;  speech |= is_sp
+ *   reason = 2 if speech and sil >= silence_after_speech, else 1 if sil >= silence_only,
+ *            else 3 if n >= max_segment, else 0
+ *   if reason: emit (t - n + 1, t, reason);  n = sil = 0;  speech = false
+ * Everything after the two flags is integer: the cuts are a function of the stream's
+ * frames, whatever the chunking, B and the other streams.
+ *
+ * state: srf_ctc_endpoint_state_bytes(B) bytes on the device (0 and a message for B < 1);
+ * reset starts every stream over.  srf_ctc_endpoint_n: logits [B][n][C], n_valid [B]
+ * (device, clamped to [0, n]), any C >= 2, the three counts >= 1, log_thr = log of a
+ * threshold in (0, 1), max_cuts >= 1.  cut_start, cut_end, cut_reason [B][max_cuts]: the
+ * segments [start, end] (inclusive, in frames since the reset) that this call closed, -1
+ * past their number; n_cuts [B]: that number.  A call that closes more than max_cuts
+ * segments of a stream stores the first max_cuts and still reports the true number; the
+ * state always runs to the end of the chunk.  n = 0 launches nothing and writes nothing. */
+size_t srf_ctc_endpoint_state_bytes(int B);
+int srf_ctc_endpoint_reset(void* state, int B, void* stream);
+int srf_ctc_endpoint_n(const float* logits, const int* n_valid, int B, int n, int C, int blank, float log_thr,
+                       int silence_only, int silence_after_speech, int max_segment, void* state, int max_cuts,
+                       int* cut_start, int* cut_end, int* cut_reason, int* n_cuts, void* stream);
 
 /* ---- MWER: expected error over an N-best list (tfsr/helper/train_helper.py
  * loss_ewerr) ----------------------------------------------------------------

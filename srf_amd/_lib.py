@@ -162,6 +162,14 @@ _SIGNATURES = {
                                                                        ctypes.POINTER(_c_int), _vp]),
     'srf_ctc_beam_lm_best': (_c_int, [_vp, _c_size] + [_c_int] * 4 + [_vp, _vp, _vp, _vp, _vp]),
     'srf_ctc_beam_lm_nbest': (_c_int, [_vp, _c_size] + [_c_int] * 6 + [_vp, _vp, _vp, _vp, _vp, _vp]),
+    'srf_ctc_beam_cut': (_c_int, [_vp, _c_size] + [_c_int] * 4 + [_vp, _c_int, _vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp,
+                                                                 _vp]),
+    'srf_ctc_beam_lm_cut': (_c_int, [_vp, _c_size] + [_c_int] * 4 + [_vp, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _c_int,
+                                                                    _vp, _vp, _vp]),
+    'srf_ctc_endpoint_state_bytes': (_c_size, [_c_int]),
+    'srf_ctc_endpoint_reset': (_c_int, [_vp, _c_int, _vp]),
+    'srf_ctc_endpoint_n': (_c_int, [_vp, _vp] + [_c_int] * 4 + [ctypes.c_float] + [_c_int] * 3 + [_vp, _c_int]
+                           + [_vp] * 5),
     'srf_mwer_workspace': (_c_size, [_c_int] * 5),
     'srf_mwer_loss': (_c_int, [_vp] * 6 + [_c_int] * 6 + [ctypes.c_float] + [_vp] * 5 + [_c_size, _vp]),
     'srf_stream_advance_n': (_c_int, [ctypes.POINTER(StreamBuf), _c_int, _c_int, _vp]),

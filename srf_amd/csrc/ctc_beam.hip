@@ -541,10 +541,9 @@ __global__ __launch_bounds__(kThreads) void ctc_beam_push_kernel(unsigned* __res
   }
 }
 
+// One utterance's block back to the single empty prefix (one lane).
 template <bool kLM>
-__global__ __launch_bounds__(64) void ctc_beam_reset_kernel(unsigned* __restrict__ state, int W, int max_frames) {
-  if (threadIdx.x != 0) return;
-  unsigned* st = state + (size_t)blockIdx.x * state_words(W, max_frames, kFieldsOf<kLM>);
+__device__ __forceinline__ void reset_utterance(unsigned* st, int W, int max_frames) {
   int* hdr = reinterpret_cast<int*>(st);
   unsigned* beam = st + kHeader;
   int* trie_parent = reinterpret_cast<int*>(beam + (size_t)kFieldsOf<kLM> * W);
@@ -568,18 +567,21 @@ __global__ __launch_bounds__(64) void ctc_beam_reset_kernel(unsigned* __restrict
   trie_parent[trie_capacity(W, max_frames)] = -1;   // label of the root
 }
 
-// One wave per utterance.  The first slot with the largest total (after a frame the beam
-// is in rank order, so slot 0); lane 0 walks the trie from its node to the root.
+template <bool kLM>
+__global__ __launch_bounds__(64) void ctc_beam_reset_kernel(unsigned* __restrict__ state, int W, int max_frames) {
+  if (threadIdx.x != 0) return;
+  reset_utterance<kLM>(state + (size_t)blockIdx.x * state_words(W, max_frames, kFieldsOf<kLM>), W, max_frames);
+}
+
+// The most probable prefix of utterance b, by one lane: the first slot with the largest
+// total (after a frame the beam is in rank order, so slot 0), its labels from a walk of the
+// trie from its node to the root.  Labels at index max_len and beyond are not stored.
 // (fused: log_prob is the ranking score, lm_score the accumulated bonus of that entry)
 template <bool kLM>
-__global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __restrict__ state, int W, int max_frames,
-                                                           int* __restrict__ labels, int* __restrict__ count,
-                                                           float* __restrict__ log_prob,
-                                                           float* __restrict__ lm_score) {
-  if (threadIdx.x != 0) return;
-  const int b = blockIdx.x;
+__device__ __forceinline__ void best_of(const unsigned* st, int b, int W, int max_frames, int max_len,
+                                        int* __restrict__ labels, int* __restrict__ count,
+                                        float* __restrict__ log_prob, float* __restrict__ lm_score) {
   const size_t cap = trie_capacity(W, max_frames);
-  const unsigned* st = state + (size_t)b * state_words(W, max_frames, kFieldsOf<kLM>);
   const int* hdr = reinterpret_cast<const int*>(st);
   const unsigned* beam = st + kHeader;
   const int* trie_parent = reinterpret_cast<const int*>(beam + (size_t)kFieldsOf<kLM> * W);
@@ -595,15 +597,63 @@ __global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __res
     }
   }
   const int len = min(max((int)beam[4 * W + best], 0), max_frames);
-  int* out = labels + (size_t)b * max_frames;
+  int* out = labels + (size_t)b * max_len;
   int node = (int)beam[best];
   for (int i = len - 1; i >= 0 && node > 0 && (size_t)node < cap; --i) {
-    out[i] = trie_label[node];
+    if (i < max_len) out[i] = trie_label[node];
     node = trie_parent[node];
   }
   count[b] = len;
   log_prob[b] = best_tot;
   if constexpr (kLM) lm_score[b] = __uint_as_float(beam[10 * W + best]);
+}
+
+// One wave per utterance; lane 0 does the work.
+template <bool kLM>
+__global__ __launch_bounds__(64) void ctc_beam_best_kernel(const unsigned* __restrict__ state, int W, int max_frames,
+                                                           int* __restrict__ labels, int* __restrict__ count,
+                                                           float* __restrict__ log_prob,
+                                                           float* __restrict__ lm_score) {
+  if (threadIdx.x != 0) return;
+  const int b = blockIdx.x;
+  best_of<kLM>(state + (size_t)b * state_words(W, max_frames, kFieldsOf<kLM>), b, W, max_frames, max_frames, labels,
+               count, log_prob, lm_score);
+}
+
+// Closing a segment.  One wave per utterance.  cut[b] >= 0: the
+// utterance's segment ends with chunk frame cut[b], which is the last frame pushed to it;
+// lane 0 writes what best would return and puts the block back to the reset state, this
+// utterance alone.  cut[b] < 0: count[b] = -1 and nothing else is touched.
+// With rest: the whole wave then copies the chunk's frames after the cut, frames
+// [cut[b] + 1, n_valid[b]), to the front of rest [b][n][C] and sets n_rest[b] to their
+// number (0 without a cut), for the push that opens the next segment.
+template <bool kLM>
+__global__ __launch_bounds__(64) void ctc_beam_cut_kernel(unsigned* __restrict__ state, int W, int max_frames,
+                                                          const int* __restrict__ cut, int max_len,
+                                                          int* __restrict__ labels, int* __restrict__ count,
+                                                          float* __restrict__ log_prob, float* __restrict__ lm_score,
+                                                          const float* __restrict__ logits,
+                                                          const int* __restrict__ n_valid, int n, int C,
+                                                          float* __restrict__ rest, int* __restrict__ n_rest) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int at = cut[b];
+  if (lane == 0) {
+    if (at < 0) {
+      count[b] = -1;
+    } else {
+      unsigned* st = state + (size_t)b * state_words(W, max_frames, kFieldsOf<kLM>);
+      best_of<kLM>(st, b, W, max_frames, max_len, labels, count, log_prob, lm_score);
+      reset_utterance<kLM>(st, W, max_frames);
+    }
+  }
+  if (!rest) return;
+  const int nv = max(0, min(n_valid[b], n));
+  const int first = at < 0 ? 0 : min(at, n - 1) + 1;   // (at < n by contract; clamped, the copy stays inside the chunk)
+  const int left = at < 0 ? 0 : max(0, nv - first);
+  if (lane == 0) n_rest[b] = left;
+  const float* src = logits + ((size_t)b * n + first) * C;
+  float* dst = rest + (size_t)b * n * C;
+  for (int i = lane; i < left * C; i += 64) dst[i] = src[i];
 }
 
 // The N first beam entries of each utterance.  After a frame the beam lies in rank order
@@ -736,6 +786,23 @@ int best(const char* what, const void* state, size_t state_bytes, int B, int C, 
 }
 
 template <bool kLM>
+int cut(const char* what, void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+        const int* cut_at, int max_len, int* labels, int* count, float* log_prob, float* lm_score, const float* logits,
+        const int* n_valid, int n, float* rest, int* n_rest, void* stream) {
+  SRF_BEAM_SHAPE(what, kFieldsOf<kLM>);
+  SRF_REQUIRE(max_len >= 1, "%s: need max_len >= 1, got %d", what, max_len);
+  SRF_REQUIRE(state && cut_at && labels && count && log_prob && (lm_score || !kLM), "%s: null pointer argument", what);
+  SRF_REQUIRE(!rest || (logits && n_valid && n_rest && n >= 1),
+              "%s: the frames after the cut need logits, n_valid, n_rest and n >= 1 (n=%d)", what, n);
+  SRF_BEAM_BYTES(what, kFieldsOf<kLM>);
+  hipLaunchKernelGGL(ctc_beam_cut_kernel<kLM>, dim3((unsigned)B), dim3(64), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned*>(state), beam_width, max_frames, cut_at, max_len, labels, count, log_prob,
+                     lm_score, logits, n_valid, n, C, rest, n_rest);
+  SRF_LAUNCH_CHECK(what);
+  return SRF_OK;
+}
+
+template <bool kLM>
 int nbest(const char* what, const void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames, int N,
           int max_len, int* labels, int* count, float* log_prob, float* lm_score, int* n_hyp, void* stream) {
   SRF_BEAM_SHAPE(what, kFieldsOf<kLM>);
@@ -780,6 +847,22 @@ extern "C" int srf_ctc_beam_nbest(const void* state, size_t state_bytes, int B, 
                                   void* stream) {
   return nbest<false>("ctc_beam_nbest", state, state_bytes, B, C, beam_width, max_frames, N, max_len, labels, count,
                       log_prob, nullptr, n_hyp, stream);
+}
+
+extern "C" int srf_ctc_beam_cut(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                const int* cut_at, int max_len, int* labels, int* count, float* log_prob,
+                                const float* logits, const int* n_valid, int n, float* rest, int* n_rest,
+                                void* stream) {
+  return cut<false>("ctc_beam_cut", state, state_bytes, B, C, beam_width, max_frames, cut_at, max_len, labels, count,
+                    log_prob, nullptr, logits, n_valid, n, rest, n_rest, stream);
+}
+
+extern "C" int srf_ctc_beam_lm_cut(void* state, size_t state_bytes, int B, int C, int beam_width, int max_frames,
+                                   const int* cut_at, int max_len, int* labels, int* count, float* score,
+                                   float* lm_score, const float* logits, const int* n_valid, int n, float* rest,
+                                   int* n_rest, void* stream) {
+  return cut<true>("ctc_beam_lm_cut", state, state_bytes, B, C, beam_width, max_frames, cut_at, max_len, labels, count,
+                   score, lm_score, logits, n_valid, n, rest, n_rest, stream);
 }
 
 extern "C" size_t srf_ctc_beam_lm_state_bytes(int B, int C, int beam_width, int max_frames) {

@@ -183,9 +183,24 @@ class BeamState:
     With ``lm`` (a ``srf_amd.lm.FusedLM`` for the same classes and blank, its tables on
     this device) the language model is fused into the beam (srf_ctc_beam_lm_*, DESIGN.md
     section 17): scores are log p_ctc + the prefix's bonuses, and ``best_device()`` returns
-    a fourth tensor, the accumulated bonus."""
+    a fourth tensor, the accumulated bonus.
 
-    def __init__(self, n_utts, n_classes, blank_index, beam_width=100, max_frames=4096, device='cuda', lm=None):
+    ``segmented=True`` is for a stream without an end that an
+    endpointer cuts into segments: ``push_cut(logits, n_valid, cut)`` closes, on the device,
+    the segment of every utterance whose cut[b] >= 0 and starts its next one, that utterance
+    alone.  The bound on the trie is then the caller's: between two cuts of an utterance at
+    most ``max_frames`` frames (the endpointer's forced cut sees to that), so the host counter
+    no longer adds up -- every push gets a fresh one, ``frames_pushed`` stays 0 -- and one
+    push takes at most max_frames frames.  This holds for ``push`` called directly as well:
+    nothing on the host or the device refuses the frame that passes the bound.  An
+    utterance that gets more than max_frames frames between two cuts writes nothing outside
+    its block (the kernel stores no trie node past the capacity), but its result is then
+    wrong without a sign of it: ``count`` is the prefix's true length while the labels whose
+    nodes were not stored are missing, and their slots hold whatever the output buffer held.
+    Without ``segmented`` nothing changes."""
+
+    def __init__(self, n_utts, n_classes, blank_index, beam_width=100, max_frames=4096, device='cuda', lm=None,
+                 segmented=False):
         _check_beam_range(n_classes, blank_index, beam_width)
         if int(n_utts) < 1 or int(max_frames) < 1:
             raise ValueError(f'need n_utts >= 1 and max_frames >= 1, got {n_utts} and {max_frames}')
@@ -194,6 +209,7 @@ class BeamState:
         self.device = torch.device(device)
         _check_lm(lm, self.shape[1], self.blank)
         self.lm = lm
+        self.segmented = bool(segmented)
         self._pushed = ctypes.c_int(0)
         n_bytes = ops.ctc_beam_state_bytes(*self.shape) if lm is None else ops.ctc_beam_lm_state_bytes(*self.shape)
         self._state = torch.empty(n_bytes, device=self.device, dtype=torch.uint8)
@@ -212,11 +228,40 @@ class BeamState:
     def push(self, logits, n_valid):
         n_valid = torch.as_tensor(n_valid).to(device=self.device, dtype=torch.int32).contiguous()
         logits = logits.detach().float().contiguous()
+        pushed = ctypes.c_int(0) if self.segmented else self._pushed
         if self.lm is None:
-            ops.ctc_beam_push(self._state, self.shape, self._pushed, logits, n_valid, self.blank)
+            ops.ctc_beam_push(self._state, self.shape, pushed, logits, n_valid, self.blank)
         else:
-            ops.ctc_beam_lm_push(self._state, self.shape, self._pushed, logits, n_valid, self.blank, self.lm.bonus,
+            ops.ctc_beam_lm_push(self._state, self.shape, pushed, logits, n_valid, self.blank, self.lm.bonus,
                                  self.lm.next)
+
+    def push_cut(self, logits, n_valid, cut, max_len=None):
+        """One chunk with at most one cut per utterance, on the current stream, with no
+        host read.  ``cut`` [B] int32: the chunk frame that is the last of utterance b's
+        segment (below n_valid[b]), or -1.  The frames up to the cut are pushed, the
+        segment is closed (srf_ctc_beam_cut: its hypothesis is kept, the utterance alone
+        starts over) and the chunk's frames after the cut open the next segment, from a
+        copy shifted left per utterance that the cut kernel writes.  Returns device tensors
+        (labels [B, max_len] int32, count [B] int32, score [B] float32, lm_score [B] float32
+        or None without a model): the closed segments' best prefixes, count = -1 for an
+        utterance without a cut.  ``max_len`` bounds the label rows (labels beyond it are
+        dropped, count stays the true length); None takes max_frames."""
+        if not self.segmented:
+            raise ValueError('push_cut needs a segmented state: build it with segmented=True')
+        dev = self.device
+        n_valid = torch.as_tensor(n_valid).to(device=dev, dtype=torch.int32).contiguous()
+        cut = torch.as_tensor(cut).to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(cut.shape) != (self.shape[0],):
+            raise ValueError(f'cut must have shape ({self.shape[0]},), got {tuple(cut.shape)}')
+        logits = logits.detach().float().contiguous()
+        max_len = self.shape[3] if max_len is None else int(max_len)
+        self.push(logits, torch.where(cut >= 0, torch.minimum(cut + 1, n_valid), n_valid))
+        if logits.dim() == 3 and logits.shape[1] == 0:
+            return ops.ctc_beam_cut(self._state, self.shape, cut, max_len, lm=self.lm is not None)
+        *out, rest, n_rest = ops.ctc_beam_cut(self._state, self.shape, cut, max_len, lm=self.lm is not None,
+                                              logits=logits, n_valid=n_valid)
+        self.push(rest, n_rest)
+        return tuple(out)
 
     def best_device(self):
         """(labels [B, max_frames] int32, count [B] int32, log_prob [B] float32), on the

@@ -884,6 +884,90 @@ def ctc_beam_lm_nbest(state, shape, n, max_len):
     return labels, count, score, n_hyp, lm_score
 
 
+def ctc_beam_cut(state, shape, cut, max_len, lm=False, logits=None, n_valid=None):
+    """srf_ctc_beam_cut / srf_ctc_beam_lm_cut (``lm``: the fused state block): close the
+    segment of every utterance with cut[b] >= 0 (cut [B] int32 on the device) and put that
+    utterance back to the reset state.  Returns device tensors (labels [B, max_len] int32,
+    count [B] int32, -1 without a cut, score [B] float32, lm_score [B] float32 or None
+    unfused).  With ``logits`` [B, n, C] and ``n_valid`` [B] the chunk's frames after each
+    cut are also copied to the front of a new buffer: the result then ends with (rest
+    [B, n, C], n_rest [B] int32)."""
+    B, C = shape[0], shape[1]
+    max_len = int(max_len)
+    if max_len < 1:
+        raise ValueError(f'max_len must be at least 1, got {max_len}')
+    _check_i32('cut', cut, (B,))
+    dev = state.device
+    labels = torch.empty((B, max_len), device=dev, dtype=torch.int32)
+    count = torch.empty(B, device=dev, dtype=torch.int32)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    lm_score = torch.empty(B, device=dev, dtype=torch.float32) if lm else None
+    rest = n_rest = None
+    n = 0
+    if logits is not None:
+        n = logits.shape[1] if logits.dim() == 3 else -1
+        _check_dev('logits', logits, (B, n, C))
+        _check_i32('n_valid', n_valid, (B,))
+        rest = torch.empty_like(logits)
+        n_rest = torch.empty(B, device=dev, dtype=torch.int32)
+    tail = [_opt_ptr(logits), _opt_ptr(n_valid), n, _opt_ptr(rest), _opt_ptr(n_rest), _stream()]
+    args = _beam_state_args(state, shape)
+    if lm:
+        _lib.check(_lib.lib().srf_ctc_beam_lm_cut(*args, _ptr(cut), max_len, _ptr(labels), _ptr(count), _ptr(score),
+                                                  _ptr(lm_score), *tail), 'srf_ctc_beam_lm_cut')
+    else:
+        _lib.check(_lib.lib().srf_ctc_beam_cut(*args, _ptr(cut), max_len, _ptr(labels), _ptr(count), _ptr(score),
+                                               *tail), 'srf_ctc_beam_cut')
+    out = (labels, count, score, lm_score)
+    return out if logits is None else out + (rest, n_rest)
+
+
+def ctc_endpoint_state(B, device):
+    """A reset endpointer state for B streams (srf_ctc_endpoint_state_bytes, _reset)."""
+    n = _lib.lib().srf_ctc_endpoint_state_bytes(int(B))
+    if n == 0:
+        _lib.check(-1, 'srf_ctc_endpoint_state_bytes')
+    state = torch.empty(n, device=device, dtype=torch.uint8)
+    ctc_endpoint_reset(state, B)
+    return state
+
+
+def ctc_endpoint_reset(state, B):
+    """srf_ctc_endpoint_reset: every stream back at its start."""
+    if not state.is_cuda or state.dtype != torch.uint8 or not state.is_contiguous():
+        raise ValueError('the endpointer state must be a contiguous uint8 device tensor')
+    _lib.check(_lib.lib().srf_ctc_endpoint_reset(_ptr(state), int(B), _stream()), 'srf_ctc_endpoint_reset')
+
+
+def ctc_endpoint(logits, n_valid, blank, log_thr, counts, state, max_cuts):
+    """srf_ctc_endpoint_n on one chunk of logits [B, n, C] (the first n_valid[b] frames of
+    stream b): counts = (silence_only, silence_after_speech, max_segment), log_thr = log of
+    the blank threshold.  Returns device tensors (cut_start, cut_end, cut_reason
+    [B, max_cuts] int32, -1 past n_cuts [B] int32)."""
+    B, n, C = logits.shape
+    _check_dev('logits', logits, (B, n, C))
+    _check_i32('n_valid', n_valid, (B,))
+    max_cuts = int(max_cuts)
+    if max_cuts < 1:
+        raise ValueError(f'max_cuts must be at least 1, got {max_cuts}')
+    if not state.is_cuda or state.dtype != torch.uint8 or not state.is_contiguous():
+        raise ValueError('the endpointer state must be a contiguous uint8 device tensor')
+    need = _lib.lib().srf_ctc_endpoint_state_bytes(B)
+    if state.numel() < need:
+        raise ValueError(f'the endpointer state holds {state.numel()} bytes, {B} streams need {need}')
+    dev = logits.device
+    if n == 0:   # nothing launches: no frame, no cut
+        out = [torch.full((B, max_cuts), -1, device=dev, dtype=torch.int32) for _ in range(3)]
+        return out[0], out[1], out[2], torch.zeros(B, device=dev, dtype=torch.int32)
+    start, end, reason = (torch.empty((B, max_cuts), device=dev, dtype=torch.int32) for _ in range(3))
+    n_cuts = torch.empty(B, device=dev, dtype=torch.int32)
+    so, sas, ms = (int(c) for c in counts)
+    _lib.check(_lib.lib().srf_ctc_endpoint_n(_ptr(logits), _ptr(n_valid), B, n, C, int(blank), float(log_thr), so, sas,
+                                             ms, _ptr(state), max_cuts, _ptr(start), _ptr(end), _ptr(reason),
+                                             _ptr(n_cuts), _stream()), 'srf_ctc_endpoint_n')
+    return start, end, reason, n_cuts
+
+
 def mwer_loss_and_grad(logits, logit_len, hyp, hyp_len, n_hyp, err, blank, grad_scale, want_grad=True):
     """srf_mwer_loss: the expected error of each utterance over its hypothesis list and
     grad_scale * its logit gradient.  logits [B, T, C] float32, logit_len [B], hyp

@@ -118,10 +118,21 @@ class StreamOut:
     stream.  ``logits`` [B, m, C] (device); ``labels``: per stream, the greedy labels
     these frames added; ``label_frames``: per stream, the global output frame at which
     each of those labels was emitted, the first frame of its arg-max run (both fetched
-    from the device together, on first use)."""
+    from the device together, on first use).  From a router with an endpointer,
+    ``segments``: per stream, the ``endpoint.Segment``s this step closed (fetched with the
+    labels)."""
 
     def __init__(self, router, t0, logits):
         self._router, self.t0, self.logits, self._labels, self._frames = router, t0, logits, None, None
+        self._segments = None
+
+    @property
+    def segments(self):
+        if self._router._ep is None:
+            raise ValueError('this router does not segment its streams: build it with endpoint=EndpointRules(...)')
+        if self._segments is None:
+            self._router._fetch_labels()
+        return [list(s) for s in self._segments]
 
     @property
     def labels(self):
@@ -169,10 +180,29 @@ class StreamingRouter:
     samples, and feeds ``resample.ResampleStream`` -> ``FbankStream`` -> ``push``.  One call
     then takes at most ``audio_bound`` input samples, the largest chunk whose outputs cannot
     exceed audio_chunk_bound(max_chunk); ``lookahead_audio_ms`` grows by the filter's half
-    width, 6000 / (0.99 min(fin, fout)) ms."""
+    width, 6000 / (0.99 min(fin, fout)) ms.
+
+    With ``endpoint`` (an ``srf_amd.endpoint.EndpointRules``) the
+    decoders are segmented per stream, on the device, with no host synchronisation in the
+    chunk step: every step's logits go through an ``endpoint.Endpointer``, and where it
+    closes a stream's segment the beam search of that stream alone starts over
+    (``ctc.BeamState.push_cut``).  ``segments`` (and ``StreamOut.segments`` for one step)
+    are, per stream, the ``endpoint.Segment``s closed so far: bounds, reason, the greedy
+    labels whose emission frame (``label_frames``) lies in [start, end] -- a label run that
+    crosses a forced cut belongs to the earlier segment, the one its first frame lies in --
+    and the beam's best prefix of the segment with its score.  ``finish()`` closes every
+    stream's open remainder as a last segment with reason 0.  ``beam_hypotheses`` is then the
+    open segment's hypothesis, ``hypotheses`` stays the whole stream's.  The model is not
+    restarted, so a stream may run without an end: the forced cut at ``max_segment`` frames
+    bounds the beam's trie, and ``max_frames`` need only be max_segment + the most output
+    frames one step emits.  The rules' smallest count must be at least that many frames, so
+    that at most one cut per stream falls into a step.  What does grow with the stream are
+    the host lists behind ``segments`` and ``hypotheses`` (and the steps' device results
+    until something is fetched): ``pop_segments()`` hands the closed segments over and drops
+    them and their labels."""
 
     def __init__(self, model, n_streams, max_chunk=64, beam_width=None, max_frames=None, lm=None, frontend=None,
-                 resampler=None):
+                 resampler=None, endpoint=None):
         if model.caps_type == 'einsum':
             raise ValueError('the einsum variant cannot stream: its positional encoding needs the absolute frame '
                              'index, which srf_primary_caps_fwd_ex does not take')
@@ -223,9 +253,29 @@ class StreamingRouter:
         # with a beam width: the device prefix beam search next to the greedy decoder, its
         # beams carried from chunk to chunk (at most max_frames output frames per stream)
         self._beam = None
+        max_frames = 4096 if max_frames is None else int(max_frames)
+        # with an endpointer: the decoders are cut into segments per stream; at most one cut
+        # per stream and step, since after a cut sil and n restart at 0 and speech is false
+        # again, so the next cut needs min(counts) further frames and a step emits at most nmax
+        self._ep = None
+        if endpoint is not None:
+            from . import endpoint as ep
+            if not isinstance(endpoint, ep.EndpointRules):
+                raise ValueError(f'endpoint must be an EndpointRules, got {type(endpoint).__name__}')
+            nmax = max(self.max_chunk // 4, self.lookahead)
+            if min(endpoint.counts) < nmax:
+                raise ValueError(f'one step emits up to max(max_chunk // 4, lookahead) = {nmax} output frames: every '
+                                 f'count of the endpoint rules must be at least that, so that at most one cut per '
+                                 f'stream falls into a step; got {endpoint!r}')
+            if beam_width and max_frames < endpoint.max_segment + nmax:
+                raise ValueError(f'a segment takes up to max_segment = {endpoint.max_segment} output frames and a step '
+                                 f'up to {nmax} more: the beam search needs max_frames >= '
+                                 f'{endpoint.max_segment + nmax}, got {max_frames}')
+            self._ep = ep.Endpointer(endpoint, self.B, model.class_n, self.blank, self.device)
+            self._seg_max_len = endpoint.max_segment   # a segment's prefix has at most a label per frame
         if beam_width:
-            self._beam = ctc.BeamState(self.B, model.class_n, self.blank, beam_width,
-                                       4096 if max_frames is None else max_frames, self.device, lm=lm)
+            self._beam = ctc.BeamState(self.B, model.class_n, self.blank, beam_width, max_frames, self.device, lm=lm,
+                                       segmented=endpoint is not None)
         self._alloc()
         self.reset()
 
@@ -268,7 +318,12 @@ class StreamingRouter:
         self._finished = False
         self._hyp = [[] for _ in range(self.B)]
         self._hyp_frames = [[] for _ in range(self.B)]
-        self._pending = []      # (StreamOut, labels, frames, count) not yet fetched from the device
+        self._pending = []      # (StreamOut, labels, frames, count, cuts) not yet fetched from the device
+        self._segs = [[] for _ in range(self.B)]   # with an endpointer: the segments closed so far
+        self._seg_from = [0] * self.B              # labels of _hyp that belong to closed segments
+        self._seg_open = [0] * self.B              # first frame of each stream's open segment
+        if self._ep is not None:
+            self._ep.reset()
         if self._beam is not None:
             self._beam.reset()
         self._beam_best = None  # (labels, scores) of the frames pushed so far, once fetched
@@ -311,15 +366,96 @@ class StreamingRouter:
         self._fetch_labels()
         return [list(f) for f in self._hyp_frames]
 
+    @property
+    def segments(self):
+        """Per stream, the ``endpoint.Segment``s closed so far (fetched with the labels)."""
+        if self._ep is None:
+            raise ValueError('this router does not segment its streams: build it with endpoint=EndpointRules(...)')
+        self._fetch_labels()
+        return [list(s) for s in self._segs]
+
+    def pop_segments(self):
+        """``segments``, handed over: the closed segments are returned and forgotten, and
+        their greedy labels leave ``hypotheses`` / ``hypothesis_frames``, which from then on
+        hold the labels of the open segments alone.  The host lists otherwise grow with the
+        stream, a label per emitted label; a router that runs without an end calls this (or
+        reads every ``StreamOut``) now and then."""
+        out = self.segments
+        for b in range(self.B):
+            del self._hyp[b][:self._seg_from[b]], self._hyp_frames[b][:self._seg_from[b]]
+        self._segs = [[] for _ in range(self.B)]
+        self._seg_from = [0] * self.B
+        return out
+
     def _fetch_labels(self):
-        for out, labels, frames, count in self._pending:
+        for out, labels, frames, count, cuts in self._pending:
             labels, frames, count = labels.cpu().tolist(), frames.cpu().tolist(), count.cpu().tolist()
             out._labels = [labels[b][:count[b]] for b in range(self.B)]
             out._frames = [frames[b][:count[b]] for b in range(self.B)]
             for b in range(self.B):
                 self._hyp[b].extend(out._labels[b])
                 self._hyp_frames[b].extend(out._frames[b])
+            if self._ep is not None:
+                out._segments = self._closed(cuts)
         self._pending = []
+
+    def _take_labels(self, b, end):
+        """The greedy labels of stream b emitted up to frame ``end`` that no segment has yet."""
+        lo = hi = self._seg_from[b]
+        fr = self._hyp_frames[b]
+        while hi < len(fr) and fr[hi] <= end:
+            hi += 1
+        self._seg_from[b] = hi
+        return self._hyp[b][lo:hi]
+
+    def _closed(self, cuts):
+        """One step's cuts (device tensors) as per-stream lists of Segments, also appended to
+        ``segments``.  Called once the step's greedy labels are in ``_hyp``."""
+        bounds, beam = cuts
+        new = [[] for _ in range(self.B)]
+        if bounds is None:
+            return new
+        # [B][3]: start, end, reason of the step's one cut, -1 without
+        bounds = torch.cat([bounds.start[:, :1], bounds.end[:, :1], bounds.reason[:, :1]], dim=1).cpu().tolist()
+        if beam is not None:
+            count = beam[1].cpu().tolist()
+            labels = beam[0][:, :max(count + [1])].cpu().tolist()
+            score = beam[2].cpu().double().tolist()
+            lm_score = None if beam[3] is None else beam[3].cpu().double().tolist()
+        from .endpoint import Segment
+        for b, (start, end, reason) in enumerate(bounds):
+            if end < 0:
+                continue
+            seg = Segment(start, end, reason, self._take_labels(b, end))
+            if beam is not None:
+                seg = seg._replace(beam_labels=labels[b][:count[b]], beam_score=score[b],
+                                   lm_score=None if lm_score is None else lm_score[b])
+            new[b].append(seg)
+            self._segs[b].append(seg)
+            self._seg_open[b] = end + 1
+        return new
+
+    def _close_open_segments(self, out):
+        """At finish(): every stream's open remainder as its last segment, reason 0, from the
+        beam's best()."""
+        self._fetch_labels()
+        from .endpoint import Segment
+        beam = self._fetch_beam() if self._beam is not None else None
+        lm_score = None
+        if beam is not None and self._beam.lm is not None:
+            lm_score = self._beam.best_device()[3].cpu().double().tolist()
+        for b in range(self.B):
+            total = (self._pushed if self._lengths[b] is None else self._lengths[b]) + 3
+            start, end = self._seg_open[b], total // 4 - 1
+            if end < start:
+                continue   # the stream's last frame closed a segment: nothing is open
+            seg = Segment(start, end, 0, self._take_labels(b, end))
+            if beam is not None:
+                seg = seg._replace(beam_labels=list(beam[0][b]), beam_score=float(beam[1][b]),
+                                   lm_score=None if lm_score is None else lm_score[b])
+            out._segments[b].append(seg)
+            self._segs[b].append(seg)
+            self._seg_open[b] = end + 1
 
     # ------------------------------------------------------------------ stages
     def _local_len(self, offset, frames):
@@ -451,6 +587,7 @@ class StreamingRouter:
             out = StreamOut(self, frames_final(self._pushed, self.L, self.rpad)[-1],
                             torch.empty((self.B, 0, self.model.class_n), device=self.device, dtype=torch.float32))
             out._labels, out._frames = [[] for _ in range(self.B)], [[] for _ in range(self.B)]
+            out._segments = [[] for _ in range(self.B)]
             return out
         if n % 4:
             take = torch.cat([take, take.new_zeros((self.B, 4 - n % 4, take.shape[2]))], dim=1)
@@ -476,20 +613,24 @@ class StreamingRouter:
         with torch.no_grad():
             out = self._step(None, True)
         self._finished = True
+        if self._ep is not None:
+            self._close_open_segments(out)
         parts = [o for o in first if o.logits.shape[1]] + [out]
         if len(parts) > 1:
             self._fetch_labels()
             both = StreamOut(self, parts[0].t0, torch.cat([o.logits for o in parts], dim=1))
             both._labels = [sum((o._labels[b] for o in parts), []) for b in range(self.B)]
             both._frames = [sum((o._frames[b] for o in parts), []) for b in range(self.B)]
+            if self._ep is not None:
+                both._segments = [sum((o._segments[b] for o in parts), []) for b in range(self.B)]
             return both
         return out
 
     def _check_beam_room(self, n, finishing):
         """Refuse a step whose output frames the beam search cannot take, before anything
         advances: the router stays as it was, its hypotheses so far can be read, and
-        reset() starts over."""
-        if self._beam is None:
+        reset() starts over.  (Not with an endpointer: its forced cut bounds the trie.)"""
+        if self._beam is None or self._ep is not None:
             return
         emitted = frames_final(self._pushed + n, self.L, self.rpad, finished=finishing)[-1]
         if emitted > self._beam.shape[3]:
@@ -552,10 +693,18 @@ class StreamingRouter:
             self._advance(new_base - base, after[1] - new_base)
             self._base = new_base
         n_valid = ((self._len_dev + 3) // 4 - t0).clamp_(0, m).to(torch.int32)
+        # with an endpointer: the segments this step's frames close (at most one per stream)
+        bounds = self._ep.push(logits, n_valid, max_cuts=1) if self._ep is not None and m else None
         labels, frames, count = self._greedy(logits, n_valid, t0)
+        closed = None
         if self._beam is not None:
-            self._beam.push(logits, n_valid)
+            if bounds is None:
+                self._beam.push(logits, n_valid)
+            else:
+                # a consuming stream has consumed t0 frames, so its cut's chunk frame is end - t0; -1 without a cut
+                closed = self._beam.push_cut(logits, n_valid, (bounds.end[:, 0] - t0).clamp_(min=-1),
+                                             max_len=self._seg_max_len)
             self._beam_best = None
         out = StreamOut(self, t0, logits)
-        self._pending.append((out, labels, frames, count))
+        self._pending.append((out, labels, frames, count, (bounds, closed)))
         return out
